@@ -5,7 +5,12 @@ A "step" is one pass of the hot path (K0 scan [+ K0b block-start finder] -> K1 H
 [-> K6 cross-segment resolution] -> K4/K5 checksum -> trailer verify) over one batch of synthetic input,
 input and output resident in HBM when the timed region starts.
 
-    python bench.py [--config 2] [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--config 2] [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run generates the workload, warms up, times K steps, checks the last step's status / length / checksum
+and prints the line.  `--full` adds what takes runs of its own: every other config as a child run (the default
+config only), the CPU baseline, the host-to-host leg and the octet compare of the output against the plaintext.
+`--dump-outputs DIR` writes what the last timed step handed its caller (see dump_outputs) as .npy files.
 
   --config 2   (default) :zlib, 1 GiB of enwik-style text, Z_FULL_FLUSH every 16 KiB — the config the metric is quoted on
   --config 2s  config 2's ONE stream (seed 0x3B2 on every rank) decoded by ALL ranks together: rank r takes the octets between
@@ -56,7 +61,7 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="2", choices=CONFIGS)
     ap.add_argument("--size-mib", type=float, default=0, help="decompressed MiB of the workload (default: the config's)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the byte compare of the output (status/checksum stay)")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the byte compare of the output (status/checksum stay)")
     ap.add_argument("--no-check", action="store_true", help="experiments with deliberately wrong kernels: time only")
     ap.add_argument("--gen-workers", type=int, default=0)
     ap.add_argument("--corpus-cache", default=None, help="directory: load the workload from it if it is there, else generate "
@@ -66,8 +71,13 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"))
     ap.add_argument("--lib", default=None, help="engine library (tests: the CPU lane-emulator build)")
     ap.add_argument("--no-h2h", action="store_true", help="skip the host-to-host leg (pageable host buffers through tbz_inflate)")
-    ap.add_argument("--no-others", action="store_true", help="the default run also times every other config (one child "
-                    "process each, before this process touches the GPU) and attaches their lines as `other_configs`: skip that")
+    ap.add_argument("--no-others", action="store_true", help="with --full the default config also times every other config "
+                    "(one child process each, before this process touches the GPU) and attaches their lines as `other_configs`: "
+                    "skip that")
+    ap.add_argument("--full", action="store_true", help="also the other configs, the CPU baseline, the host-to-host leg and "
+                    "the octet compare of the output (a plain run times the steps and checks status / length / checksum)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one "
+                    "computed as DIR/results.npy and DIR/output.npy (see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -90,7 +100,7 @@ def run_other_configs():
             continue
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", c, "--steps", "5", "--warmup", "2",
-                                "--no-cpu-baseline", "--no-others"], capture_output=True, text=True, timeout=120)
+                                "--full", "--no-cpu-baseline", "--no-others"], capture_output=True, text=True, timeout=120)
             j = json.loads(r.stdout.strip().split("\n")[-1])
             rec.update({"workload": j["config"]["workload"], "value": j["value"], "unit": j["unit"],
                         "ms_per_step": j["ms_per_step"], "steps": j["steps"], "verified": True,
@@ -231,6 +241,43 @@ def k2_names(kinds):
     return "+".join(names) or "none"
 
 
+RESULT_FIELDS = ("status", "out_len", "out_total", "in_consumed", "adler32", "crc32", "trailer_check", "flags", "boundary_out")
+DUMP_WINDOWS, DUMP_WINDOW = 4096, 1024   # an output larger than 4 MiB is dumped as 4 096 windows of 1 KiB at seeded positions
+
+
+def dump_outputs(d, eng, d_out, results, lens, offs, span):
+    """--dump-outputs: what the last timed step handed its caller, so that two builds can be compared output for output.
+      results.npy  float64 [streams, 9]: the tbz_result fields RESULT_FIELDS of every stream, in stream order
+      output.npy   float32: the decoded octets of the streams laid end to end (stream i: `lens[i]` octets at device offset
+                   `offs[i]`); all of them up to DUMP_WINDOWS x DUMP_WINDOW octets, beyond that that many windows at positions
+                   drawn from a fixed seed, in position order; -1 where a stream's out_len falls short of the position.
+    The positions depend only on the workload (`lens`), never on what the engine returned."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rows = np.array([[float(getattr(r, f)) for f in RESULT_FIELDS] for r in results], dtype=np.float64).reshape(-1, len(RESULT_FIELDS))
+    np.save(os.path.join(d, "results.npy"), rows)
+    lens = np.asarray(lens, dtype=np.int64)
+    ends = np.cumsum(lens)
+    total = int(ends[-1]) if len(lens) else 0
+    if total <= DUMP_WINDOWS * DUMP_WINDOW:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        starts = np.sort(np.random.default_rng(0x3B2D).integers(0, total - DUMP_WINDOW + 1, size=DUMP_WINDOWS))
+        pos = (starts[:, None] + np.arange(DUMP_WINDOW, dtype=np.int64)[None, :]).ravel()
+    out = np.full(len(pos), -1.0, dtype=np.float32)
+    if len(pos) and span:
+        host = bytearray(span)
+        eng.d2h(host, d_out, span)
+        h = np.frombuffer(host, dtype=np.uint8)
+        i = np.searchsorted(ends, pos, side="right")
+        local = pos - (ends[i] - lens[i])
+        got = np.array([int(r.out_len) for r in results] + [0] * (len(lens) - len(results)), dtype=np.int64)
+        dev = np.asarray(list(offs) + [0] * (len(lens) - len(offs)), dtype=np.int64)[i] + local
+        ok = (local < np.minimum(got[i], lens[i])) & (dev < span)
+        out[ok] = h[dev[ok]]
+    np.save(os.path.join(d, "output.npy"), out)
+
+
 def main(argv=None):
     args = parse_args(argv)
     world_env = os.environ.get("WORLD_SIZE")
@@ -254,8 +301,9 @@ def main(argv=None):
     cfg = args.config
     mib = args.size_mib or DEFAULT_MIB[cfg]
     others = None
-    if (cfg == "2" and world == 1 and not args.size_mib and not args.lib and not args.corpus_cache and not args.no_cpu_baseline
-            and not args.no_others and not args.gen_only and not args.no_check and args.backend == "nccl"):
+    if (args.full and cfg == "2" and world == 1 and not args.size_mib and not args.lib and not args.corpus_cache
+            and not args.no_cpu_baseline and not args.no_others and not args.gen_only and not args.no_check
+            and args.backend == "nccl"):
         others = run_other_configs()
     ncpu = os.cpu_count() or 1
     workers = args.gen_workers or max(1, min(16, ncpu // max(1, world)))
@@ -414,14 +462,23 @@ def main(argv=None):
         dt = float(tt.item())
     t = eng.timings() if n else None
 
+    if args.dump_outputs and rank == 0:
+        if shard is not None:   # this rank's part of the one stream, at the start of its output
+            v = verdicts[0]
+            lens = [len(wl.streams[0][1]) if world == 1 else v["offsets"][1] - v["offsets"][0]]
+            dump_outputs(args.dump_outputs, eng, d_out, res, lens, [0], opos)
+        else:
+            dump_outputs(args.dump_outputs, eng, d_out, res if n else [], [len(p) for _, p, _ in wl.streams],
+                         member_offs[0] if blob is not None else out_offs, opos)
+
     # ---- correctness of what was timed: status, length, checksum against what the generator computed from the
-    # plaintext (and the engine's own trailer verdict), and a byte compare of the output
+    # plaintext (and the engine's own trailer verdict); with --full also a byte compare of the output
     if shard is not None and not args.no_check:
         # one stream across the ranks: the verdict of the last step (seams, total, combined checksum against the stream's own
         # trailer) and this rank's octets against its part of the plaintext
         v, (s0, p0, a0) = verdicts[0], wl.streams[0]
         assert v["ok"] and v["total"] == len(p0) and v["check"] == a0 and v["in_consumed"] == len(s0), v
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             lo = v["offsets"][rank]
             hi = v["offsets"][rank + 1] if rank + 1 < world else v["total"]
             got = bytearray(hi - lo)
@@ -436,7 +493,7 @@ def main(argv=None):
             assert r.adler32 == ck and (r.flags & 1), (i, hex(r.adler32), hex(ck))
         elif wl.fmt == "gzip":
             assert r.crc32 == ck and (r.flags & 1), (i, hex(r.crc32), hex(ck))
-    if not args.no_verify and not args.no_check and n and shard is None:
+    if args.full and not args.no_verify and not args.no_check and n and shard is None:
         got = bytearray(opos)
         eng.d2h(got, d_out, opos)
         g = np.frombuffer(got, dtype=np.uint8)
@@ -513,7 +570,7 @@ def main(argv=None):
     # tbz_inflate_batch.  Never `value`.  The ceiling beside it: what hipMemcpy moves on this box between PINNED host
     # memory and the device (torch's pinned tensors), each direction alone.
     h2h = None
-    if rank == 0 and world == 1 and n and blob is None and shard is None and not emu and not args.no_h2h:
+    if args.full and rank == 0 and world == 1 and n and blob is None and shard is None and not emu and not args.no_h2h:
         h_ins = [s for s, _, _ in wl.streams]
         h_outs = [bytearray(len(p)) for _, p, _ in wl.streams]
         def h2h_step():
@@ -561,7 +618,7 @@ def main(argv=None):
                        % ("_batch" if n > 1 else "")}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and n:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and n:
         from oracle import oracle as O
         O.lib()
         # a bounded sample: whole streams of the workload until ~1 GiB of output or the CPU budget is spent

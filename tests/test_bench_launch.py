@@ -6,19 +6,21 @@ import json
 import os
 import subprocess
 import sys
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 EMU = os.path.join(EMU_DIR, "libtbz_emu.so")
 
 
-def _run(*extra, timeout=900):
+def _run(*extra, timeout=900, full=True):
+    """full: with --full, so that the output is also compared octet for octet with the plaintext"""
     subprocess.check_call(["make", "-C", EMU_DIR, "libtbz_emu.so"], stdout=subprocess.DEVNULL)
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "gloo", "--lib", EMU,
-                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline", *extra],
+                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline", *(("--full",) if full else ()), *extra],
                        capture_output=True, text=True, env=env, timeout=timeout)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -56,3 +58,25 @@ def test_bench_one_stream_across_two_ranks():
     assert j["config"]["decompressed_bytes"] == 512 << 10 and j["value"] > 0
     j = _run("--config", "2s", "--size-mib", "0.25")     # one rank: the plan is one part, the verdict the engine's own
     assert j["n_gpus"] == 1 and j["scaling"] == "strong"
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain run (no --full) times --steps steps and prints ms_per_step; --dump-outputs writes the last step's result
+    records and its decoded octets (all of them below the sample size) as float arrays"""
+    import numpy as np
+    from tools import corpus as K
+    j = _run("--config", "1", "--steps", "3", "--dump-outputs", str(tmp_path / "c1"), full=False)
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["cpu_baseline"] is None and j["host_to_host"] is None
+    assert "other_configs" not in j
+    res, out = np.load(tmp_path / "c1" / "results.npy"), np.load(tmp_path / "c1" / "output.npy")
+    assert res.dtype == np.float64 and out.dtype == np.float32
+    _, plain = K.config1_stream()
+    assert res.shape == (1, 9) and res[0, 0] == 0 and res[0, 1] == len(plain)
+    assert np.array_equal(out, np.frombuffer(plain, dtype=np.uint8).astype(np.float32))
+    # a batch: one record per member, the members' octets end to end
+    _run("--config", "3", "--size-mib", "0.5", "--dump-outputs", str(tmp_path / "c3"), full=False)
+    res, out = np.load(tmp_path / "c3" / "results.npy"), np.load(tmp_path / "c3" / "output.npy")
+    blob, offs, plains = K.gzip_members(2, 256 << 10, seed=0x3B2)
+    assert res.shape == (2, 9) and (res[:, 0] == 0).all() and (res[:, 1] == 256 << 10).all()
+    assert [int(c) for c in res[:, 5]] == [zlib.crc32(p) for p in plains]
+    assert np.array_equal(out, np.frombuffer(b"".join(plains), dtype=np.uint8).astype(np.float32))

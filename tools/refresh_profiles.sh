@@ -6,9 +6,9 @@ COMMIT=${2:-unknown}
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
-# the headline line as a driver gets it: the plain default command (every other config attached as other_configs).  The
+# the headline line with everything: the default command with --full (every other config attached as other_configs).  The
 # profiler passes below read their workload from a private cache, generated here WITHOUT the profiler (the generators fork)
-python3 $R/bench.py > $O/${TAG}_bench.jsonl 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -5 $O/${TAG}_bench.err; exit 1; }
+python3 $R/bench.py --full > $O/${TAG}_bench.jsonl 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -5 $O/${TAG}_bench.err; exit 1; }
 python3 $R/bench.py --corpus-cache /tmp/tbz_corpus_$(id -u) --gen-only || exit 1
 tail -c 600 $O/${TAG}_bench.jsonl
 cd /tmp && export TMPDIR=/tmp
