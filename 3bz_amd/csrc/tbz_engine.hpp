@@ -479,7 +479,6 @@ struct StreamPlan {
 struct SegHost {
   Seg seg;
   Item item;  // the K1 item that produced it (re-decoded to locate a distance error exactly)
-  uint32_t stream;
   uint32_t deficit;
   bool continues;  // must share the window with the previous segment (fix-up continuation)
 };
@@ -492,6 +491,12 @@ static float elapsed(tbz_ctx* ctx, int a, int b) {
   float ms = 0;
   if (hipEventElapsedTime(&ms, ctx->ev[a], ctx->ev[b]) != hipSuccess) return 0;
   return ms;
+}
+// device -> host on the context's stream; complete when this returns
+static int read_back(tbz_ctx* ctx, void* dst, const void* src, size_t bytes) {
+  TBZ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  TBZ_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 // checksum of out[out_off .. +len) per stream on the device; kind 1 = adler32, 2 = crc32
@@ -541,9 +546,7 @@ static int run_checksums(tbz_ctx* ctx, int kind, const void* d_out, const std::v
   }
   TBZ_HIP(hipGetLastError());
   out.resize(n);
-  TBZ_HIP(hipMemcpyAsync(out.data(), ctx->d_ck_out.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  TBZ_HIP(hipStreamSynchronize(ctx->stream));
-  return 0;
+  return read_back(ctx, out.data(), ctx->d_ck_out.p, n * sizeof(uint32_t));
 }
 
 // adler32 from the per-group partials the two-wave K2 leaves behind (it takes them from its LDS window while the
@@ -582,9 +585,7 @@ static int run_adler_groups(tbz_ctx* ctx, const std::vector<uint32_t>& first_gro
   TBZ_LAUNCH(tbz_k4_adler_combine, n, ctx->stream, c);
   TBZ_HIP(hipGetLastError());
   out.resize(n);
-  TBZ_HIP(hipMemcpyAsync(out.data(), ctx->d_ck_out.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  TBZ_HIP(hipStreamSynchronize(ctx->stream));
-  return 0;
+  return read_back(ctx, out.data(), ctx->d_ck_out.p, n * sizeof(uint32_t));
 }
 
 // what a resumable session (tbz_session_*) and the allocate-once entry point ask of the pipeline beyond a plain call;
@@ -659,6 +660,39 @@ static int small_fused_try(tbz_ctx* ctx, int format, const void* d_in, uint64_t 
   return 0;
 }
 
+// groups whose whole output fits a linear LDS window (the common case: flush-delimited segments) run with dynamic LDS
+// sized to the largest of them (max_out octets)
+static void launch_k2_linear(tbz_ctx* ctx, K2Params& k2, size_t n_groups, uint64_t max_out) {
+  k2.win_bytes = (u32)((max_out + K2_SLACK + 63) & ~63ull);
+  ctx->tim.k2_kinds |= ctx->k2_single ? 2u : 1u;
+  if (ctx->k2_single)
+    TBZ_LAUNCH_DYN(tbz_k2_lz77_small, n_groups, k2.win_bytes + 2 * K2_TOKBUF + 512, ctx->stream, k2);
+  else
+    TBZ_LAUNCH_DYN_WG(tbz_k2_lz77_dual, n_groups, 128, k2.win_bytes + 2 * K2_TOKBUF + 512 + 2 * sizeof(K2Hand),
+                      ctx->stream, k2);
+}
+// the rest take the 32 KiB-history ring kernel (nwg workgroups)
+static void launch_k2_ring(tbz_ctx* ctx, const K2Params& k2, size_t nwg) {
+  ctx->tim.k2_kinds |= 4u;
+  if (ctx->k2_single) TBZ_LAUNCH(tbz_k2_lz77, nwg, ctx->stream, k2);
+  else if (ctx->k2_ring2) TBZ_LAUNCH_WG(tbz_k2_lz77_ring2, nwg, 128, ctx->stream, k2);
+  else TBZ_LAUNCH_WG(tbz_k2_lz77_ring3, nwg, 192, ctx->stream, k2);
+}
+// experiment builds: the linear kernel's counters and records (TBZ_K2_TRACE)
+static void k2_trace(tbz_ctx* ctx) {
+#ifdef TBZ_WAVE_TRACE
+  if (const char* vp = getenv("TBZ_K2_TRACE")) {
+    std::vector<u64> h(8192 * 8);
+    hipStreamSynchronize(ctx->stream);
+    u32 cn[4] = {0, 0, 0, 0};
+    hipMemcpyFromSymbol(cn, HIP_SYMBOL(tbz_dbg_cnt), 16);
+    fprintf(stderr, "tbz: K2 resolve since the start: %u batches with matches, %.2f rounds and %.1f matches per batch\n", cn[0],
+            cn[0] ? (double)cn[1] / cn[0] : 0.0, cn[0] ? (double)cn[2] / cn[0] : 0.0);
+    hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(tbz_dbg), h.size() * 8);
+    if (FILE* f = fopen(vp, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+  }
+#endif
+}
 // An H-group is a group decoded in parallel with the groups before it: its matches may reach into output
 // that does not exist yet.  hgs = the H-groups of the call in output order; the launch list holds n_small groups for the
 // linear kernels (launched by the caller), then n_big plain large groups, then the n_h H-groups.
@@ -773,14 +807,9 @@ static int hgroups_launch(tbz_ctx* ctx, const std::vector<HGroupSpan>& hgs, K2Pa
   k2.n_plain = (u32)n_big;
   k2.mark_base = (u8*)ctx->d_mark.p + m0;
   k2.mark_bias = mark_lo;
-  ctx->tim.k2_kinds |= 4u | 8u;
+  ctx->tim.k2_kinds |= 8u;
   ctx->tim.n_hgroups = n_h;
-  {
-    const size_t nwg = n_big + 2 * n_h;
-    if (ctx->k2_single) TBZ_LAUNCH(tbz_k2_lz77, nwg, ctx->stream, k2);
-    else if (ctx->k2_ring2) TBZ_LAUNCH_WG(tbz_k2_lz77_ring2, nwg, 128, ctx->stream, k2);
-    else TBZ_LAUNCH_WG(tbz_k2_lz77_ring3, nwg, 192, ctx->stream, k2);
-  }
+  launch_k2_ring(ctx, k2, n_big + 2 * n_h);
   TBZ_HIP(hipEventRecord(ctx->ev[10], ctx->stream));
   const K6Range* dr = (const K6Range*)ctx->d_hg.p;
   const K6List* dl = (const K6List*)ctx->d_k6s.p;
@@ -820,70 +849,141 @@ static int hgroups_launch(tbz_ctx* ctx, const std::vector<HGroupSpan>& hgs, K2Pa
   return 0;
 }
 
-// the whole pipeline on device-resident buffers
-static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, const uint64_t* in_offs,
-                        const uint64_t* in_lens, void* d_out, const uint64_t* out_offs, const uint64_t* out_caps,
-                        tbz_result* results, bool size_only, CoreOpts* opt = nullptr) {
-  if (!ctx || !results || (n && (!in_offs || !in_lens))) return TBZ_E_ARG;
-  if (format < 0 || format > 2) return TBZ_E_ARG;
-  if (!size_only && n && (!out_offs || !out_caps)) return TBZ_E_ARG;
+// ==================================================================================================== inflate_core
+// The whole pipeline on device-resident buffers, run as a sequence of stages over one `Call`: the call's arguments,
+// what follows from them, and the state that passes from one stage to the next.  Each stage returns 0 or a TBZ_E_* code.
+enum { DIST_NONE = 0, DIST_FIRST = 1, DIST_AFTER_OVERFLOW = 2 };  // per stream: a match reaching before its first octet
+struct Call {
+  // ---- the arguments
+  tbz_ctx* ctx;
+  int format;
+  size_t n;
+  const void* d_in;
+  const uint64_t *in_offs, *in_lens;
+  void* d_out;  // (CoreOpts::alloc: set once the size is known)
+  const uint64_t *out_offs, *out_caps;
+  tbz_result* results;
+  bool size_only;
+  CoreOpts* opt;
+  // ---- derived from them
+  uint64_t hist_len = 0;
+  uint32_t bit_off = 0;
+  uint64_t resume_abs = 0;
+  // ---- K0 / K0b / K0c: the stream table, the markers (flush points, block-start candidates), the K1 items built from them
+  std::vector<StreamPlan> sp;
+  uint64_t tiles = 0, in_lo = ~0ull, in_extent = 0, in_total_bits = 0;
+  uint32_t n_mark = 0, n_fixed_items = 0;  // flush markers; how many of them are followed by a fixed-Huffman block
+  uint32_t n_stored_heads = 0;             // streams that begin with a stored block
+  std::vector<uint32_t> first_marker;      // [n + 1]
+  const u64* d_markers_cur = nullptr;      // the list the items were built from, and its per-stream starts
+  const u32* d_first_marker = nullptr;
+  size_t n_items = 0;                      // n_mark + n (fixed from the pools on)
+  std::vector<Item> items;                 // host copy of the items (the general layout path; empty: not fetched yet)
+  bool have_find = false;                  // K0b / K0c ran (events 8 / 9)
+  // ---- K1: the token pools (see call_pools), the flavour's choices
+  uint64_t pool_base = 0, pool2_base = 0, pool2_hi = 0;
+  u32 half1 = 0, half2 = 0;  // log2 of the input bits per token word of the call's pool / the repair pool
+  bool wide_beside = false;  // the main launch's large items were decoded by gangs of 64 on the second stream (d_wide_res)
+  float huff_ms = 0;
+  // ---- K3: the device layout and its verdict
+  bool simple = false;
+  K3Params k3{};  // (k3.n_tiles: K3's tiles)
+  K3Global* h_glob = nullptr;  // (pinned read-backs)
+  K3Stream* h_k3s = nullptr;
+  bool fused_adler = false;    // adler32 partials come from K2 (simple path, zlib, all groups in the two-wave kernel)
+  // ---- the general (host) layout path
+  std::vector<std::vector<SegHost>> per_stream;
+  std::vector<uint8_t> dist_first;  // DIST_*
+  uint64_t dist_at = ~0ull;         // (sessions: one stream)
+  std::vector<Seg> h_segs;
+  std::vector<Group> h_groups;
+  std::vector<uint8_t> h_hist;      // per group: 1 = H-group (symbolic history)
+  std::vector<uint32_t> h_gstream;  // per group: its stream
+  std::vector<int32_t> h_grec;      // per group: index of the slice record that describes it (tbz_k3_slice), or -1
+  std::vector<BigSeg> bigs;
+  uint32_t n_recs = 0;
+};
+
+// ---------------------------------------------------------------- argument checks, reset, the one-launch path
+// *done: nothing more to do (no streams, or the one-launch path decoded the call)
+static int call_begin(Call& c, bool* done) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
+  CoreOpts* opt = c.opt;
+  *done = true;
+  if (!ctx || !c.results || (n && (!c.in_offs || !c.in_lens))) return TBZ_E_ARG;
+  if (c.format < 0 || c.format > 2) return TBZ_E_ARG;
+  if (!c.size_only && n && (!c.out_offs || !c.out_caps)) return TBZ_E_ARG;
   if (opt && n != 1) return TBZ_E_ARG;
-  const uint64_t hist_len = opt ? opt->hist_len : 0;
-  if (hist_len && !ctx->sym_hist) return TBZ_E_UNSUPPORTED;  // (TBZ_HIST=off: no way to reach octets of an earlier call)
-  const uint32_t bit_off = opt ? opt->start_bit_off : 0;
-  const uint64_t resume_abs = (opt && opt->resume_tok_bit && n) ? in_offs[0] * 8 + opt->resume_tok_bit : 0;
+  c.hist_len = opt ? opt->hist_len : 0;
+  if (c.hist_len && !ctx->sym_hist) return TBZ_E_UNSUPPORTED;  // (TBZ_HIST=off: no way to reach octets of an earlier call)
+  c.bit_off = opt ? opt->start_bit_off : 0;
+  c.resume_abs = (opt && opt->resume_tok_bit && n) ? c.in_offs[0] * 8 + opt->resume_tok_bit : 0;
   TBZ_HIP(hipSetDevice(ctx->device));
   ctx->tim = tbz_timings{};
   ctx->gang_rounds = ctx->gang_valid = 0;
-  for (size_t i = 0; i < n; i++) memset(&results[i], 0, sizeof(tbz_result));
+  for (size_t i = 0; i < n; i++) memset(&c.results[i], 0, sizeof(tbz_result));
   if (n == 0) return 0;
   if (n > 0x7fffffffu) return TBZ_E_ARG;
-  int r;
   // one small stream, an ordinary one-shot call, the engine's own flavours: the one-launch path first
-  if (n == 1 && !opt && !size_only && ctx->small_fused && in_lens[0] && in_lens[0] <= ctx->small_max_in && d_in && (d_out || !out_caps[0]) &&
-      !ctx->k1_mode && ctx->find_mode == 1 && !ctx->host_layout && !ctx->k2_single && ctx->sym_hist && !ctx->tun.tok_full) {
+  if (n == 1 && !opt && !c.size_only && ctx->small_fused && c.in_lens[0] && c.in_lens[0] <= ctx->small_max_in && c.d_in &&
+      (c.d_out || !c.out_caps[0]) && !ctx->k1_mode && ctx->find_mode == 1 && !ctx->host_layout && !ctx->k2_single &&
+      ctx->sym_hist && !ctx->tun.tok_full) {
     bool handled = false;
-    if ((r = small_fused_try(ctx, format, (const uint8_t*)d_in + in_offs[0], in_lens[0], d_out ? (uint8_t*)d_out + out_offs[0] : nullptr,
-                             out_caps[0], &results[0], &handled)))
+    int r;
+    if ((r = small_fused_try(ctx, c.format, (const uint8_t*)c.d_in + c.in_offs[0], c.in_lens[0],
+                             c.d_out ? (uint8_t*)c.d_out + c.out_offs[0] : nullptr, c.out_caps[0], &c.results[0], &handled)))
       return r;
     if (handled) return 0;
     ctx->tim = tbz_timings{};
   }
+  *done = false;
+  return 0;
+}
 
-  // ---------------------------------------------------------------- stream table + tiles
-  std::vector<StreamPlan> sp(n);
-  std::vector<uint64_t> h_off(n), h_len(n);
-  std::vector<uint32_t> tile_first(n + 1);
-  uint64_t in_extent = 0, in_lo = ~0ull, tiles = 0, in_total_bits = 0;
-  for (size_t s = 0; s < n; s++) {
-    sp[s].in_off = in_offs[s];
-    sp[s].in_len = in_lens[s];
-    sp[s].out_off = size_only ? 0 : out_offs[s];
-    sp[s].out_cap = size_only ? ~0ull : out_caps[s];
-    h_off[s] = in_offs[s];
-    h_len[s] = in_lens[s];
-    in_extent = std::max(in_extent, in_offs[s] + in_lens[s]);
-    if (in_lens[s]) in_lo = std::min(in_lo, in_offs[s]);
-    in_total_bits += in_lens[s] * 8;
-    tile_first[s] = (uint32_t)tiles;
-    // tiles are 64 KiB of memory starting at the stream's first octet rounded down to 16 (see K0)
-    tiles += ((((uintptr_t)d_in + in_offs[s]) & 15) + in_lens[s] + SCAN_TILE - 1) / SCAN_TILE;
-    if (tiles > 0x7fffffffu) return TBZ_E_ARG;
+// the items of stream s: its head item, then one per marker (how tbz_k0_items lays them out)
+static void set_item_ranges(Call& c) {
+  for (size_t s = 0; s < c.n; s++) {
+    StreamPlan& S = c.sp[s];
+    S.first_marker = c.first_marker[s];
+    S.first_item = c.first_marker[s] + (uint32_t)s;
+    S.n_items = 1 + (c.first_marker[s + 1] - c.first_marker[s]);
+    S.cur_item = S.first_item;
   }
-  tile_first[n] = (uint32_t)tiles;
-  if (in_extent && !d_in) return TBZ_E_ARG;
+}
 
+// ---------------------------------------------------------------- K0: stream table, tiles, markers + items
+// One pass over the input finds the markers (kept per tile, then compacted in order) and a small kernel
+// builds the K1 items; the host reads 8 bytes + one index per stream.  Host copies of the marker and item
+// arrays are fetched only by the general (host) layout path.
+static int call_k0(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
+  std::vector<uint32_t> tile_first(n + 1);
+  c.sp.resize(n);
+  c.first_marker.assign(n + 1, 0);
+  for (size_t s = 0; s < n; s++) {
+    StreamPlan& S = c.sp[s];
+    S.in_off = c.in_offs[s];
+    S.in_len = c.in_lens[s];
+    S.out_off = c.size_only ? 0 : c.out_offs[s];
+    S.out_cap = c.size_only ? ~0ull : c.out_caps[s];
+    c.in_extent = std::max(c.in_extent, c.in_offs[s] + c.in_lens[s]);
+    if (c.in_lens[s]) c.in_lo = std::min(c.in_lo, c.in_offs[s]);
+    c.in_total_bits += c.in_lens[s] * 8;
+    tile_first[s] = (uint32_t)c.tiles;
+    // tiles are 64 KiB of memory starting at the stream's first octet rounded down to 16 (see K0)
+    c.tiles += ((((uintptr_t)c.d_in + c.in_offs[s]) & 15) + c.in_lens[s] + SCAN_TILE - 1) / SCAN_TILE;
+    if (c.tiles > 0x7fffffffu) return TBZ_E_ARG;
+  }
+  tile_first[n] = (uint32_t)c.tiles;
+  if (c.in_extent && !c.d_in) return TBZ_E_ARG;
+  const size_t tiles = c.tiles;
+  int r;
   if ((r = record(ctx, 0))) return r;
-  // ---------------------------------------------------------------- K0: markers + items, on the device
-  // One pass over the input finds the markers (kept per tile, then compacted in order) and a small kernel
-  // builds the K1 items; the host reads 8 bytes + one index per stream.  Host copies of the marker and item
-  // arrays are fetched only by the general (host) layout path.
-  std::vector<Item> items;
-  bool host_tables = false, have_find = false, have_resolve = false;
-  uint32_t n_mark = 0, n_fixed_items = 0;  // flush markers; how many of them are followed by a fixed-Huffman block
-  uint32_t n_stored_heads = 0;             // streams that begin with a stored block
-  std::vector<uint32_t> first_marker(n + 1, 0);
+  if ((r = pinned(ctx, (n + 5) * 4 + 16 + sizeof(K3Global) + (n + 1) * sizeof(K3Stream)))) return r;  // (read-backs, K0 to K3)
   if (tiles) {
+    const std::vector<uint64_t> h_off(c.in_offs, c.in_offs + n), h_len(c.in_lens, c.in_lens + n);
     if ((r = upload(ctx, ctx->d_str_off, h_off))) return r;
     if ((r = upload(ctx, ctx->d_str_len, h_len))) return r;
     if ((r = upload(ctx, ctx->d_tile_first, tile_first))) return r;
@@ -893,558 +993,489 @@ static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, co
     if ((r = ensure(ctx, ctx->d_markers, tiles * (size_t)K0_SLOTS * 8 + 16))) return r;
     if ((r = ensure(ctx, ctx->d_k0_fm, (n + 1) * 4 + 16))) return r;  // [0..1] head, [2..] first_marker, [n+3] fixed-block items, [n+4] stored heads
     if ((r = ensure(ctx, ctx->d_items, (tiles * (size_t)K0_SLOTS + n) * sizeof(Item)))) return r;
-    if ((r = pinned(ctx, (n + 5) * 4 + 16 + sizeof(K3Global) + (n + 1) * sizeof(K3Stream)))) return r;
-    K0Params k0{(const u8*)d_in, (const u64*)ctx->d_str_off.p, (const u64*)ctx->d_str_len.p,
+    K0Params k0{(const u8*)c.d_in, (const u64*)ctx->d_str_off.p, (const u64*)ctx->d_str_len.p,
                 (const u32*)ctx->d_tile_first.p, (u32)n, (u32)tiles, (u32*)ctx->d_tile_counts.p,
                 (u32*)ctx->d_tile_offsets.p, (u64*)ctx->d_markers.p, (u64*)ctx->d_k0_slots.p,
-                (u32*)ctx->d_k0_fm.p + 2, (u32*)ctx->d_k0_fm.p, (Item*)ctx->d_items.p, (u32)format, 0, bit_off,
-                (u32*)ctx->d_k0_fm.p + (n + 3), resume_abs ? 1u : 0u};
+                (u32*)ctx->d_k0_fm.p + 2, (u32*)ctx->d_k0_fm.p, (Item*)ctx->d_items.p, (u32)c.format, 0, c.bit_off,
+                (u32*)ctx->d_k0_fm.p + (n + 3), c.resume_abs ? 1u : 0u};
     const size_t max_items = tiles * (size_t)K0_SLOTS + n;
     TBZ_LAUNCH(tbz_k0_scan_tiles, tiles, ctx->stream, k0);
     TBZ_LAUNCH_WG(tbz_k0_scan_offsets, 1, K0_SCAN_THREADS, ctx->stream, k0);
     TBZ_LAUNCH(tbz_k0_compact, tiles, ctx->stream, k0);
     TBZ_LAUNCH(tbz_k0_items, (max_items + 63) / 64, ctx->stream, k0);
     uint32_t* h_head = (uint32_t*)ctx->h_pin;
-    TBZ_HIP(hipMemcpyAsync(h_head, ctx->d_k0_fm.p, (n + 5) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TBZ_HIP(hipStreamSynchronize(ctx->stream));
-    n_mark = h_head[0];
-    n_fixed_items = h_head[n + 3];
-    n_stored_heads = h_head[n + 4];
-    for (size_t s = 0; s <= n; s++) first_marker[s] = h_head[2 + s];
+    if ((r = read_back(ctx, h_head, ctx->d_k0_fm.p, (n + 5) * 4))) return r;
+    c.n_mark = h_head[0];
+    c.n_fixed_items = h_head[n + 3];
+    c.n_stored_heads = h_head[n + 4];
+    for (size_t s = 0; s <= n; s++) c.first_marker[s] = h_head[2 + s];
     if (h_head[1]) {  // a tile with more markers than slots: the second, emitting pass
-      if ((r = ensure(ctx, ctx->d_markers, (size_t)n_mark * 8 + 16))) return r;
-      if ((r = ensure(ctx, ctx->d_items, ((size_t)n_mark + n) * sizeof(Item)))) return r;
+      if ((r = ensure(ctx, ctx->d_markers, (size_t)c.n_mark * 8 + 16))) return r;
+      if ((r = ensure(ctx, ctx->d_items, ((size_t)c.n_mark + n) * sizeof(Item)))) return r;
       k0.markers = (u64*)ctx->d_markers.p;
       k0.items = (Item*)ctx->d_items.p;
       k0.second_pass = 1;
       TBZ_LAUNCH(tbz_k0_scan_emit, tiles, ctx->stream, k0);
-      TBZ_LAUNCH(tbz_k0_items, ((size_t)n_mark + n + 63) / 64, ctx->stream, k0);
+      TBZ_LAUNCH(tbz_k0_items, ((size_t)c.n_mark + n + 63) / 64, ctx->stream, k0);
     }
     TBZ_HIP(hipGetLastError());
-    for (size_t s = 0; s < n; s++) {
-      StreamPlan& S = sp[s];
-      S.first_marker = first_marker[s];
-      S.first_item = first_marker[s] + (uint32_t)s;
-      S.n_items = 1 + (first_marker[s + 1] - first_marker[s]);
-      S.cur_item = S.first_item;
-    }
   } else {
     // nothing to scan (every stream empty): one head item per stream, built here
     if ((r = ensure(ctx, ctx->d_markers, 16))) return r;
     if ((r = ensure(ctx, ctx->d_k0_fm, (n + 1) * 4 + 8))) return r;
     std::vector<uint32_t> zero(n + 3, 0);
     if ((r = upload(ctx, ctx->d_k0_fm, zero))) return r;
-    if ((r = pinned(ctx, (n + 5) * 4 + 16 + sizeof(K3Global) + (n + 1) * sizeof(K3Stream)))) return r;
     for (size_t s = 0; s < n; s++) {
-      StreamPlan& S = sp[s];
       Item it{};
-      it.start_bit = S.in_off * 8 + (s == 0 ? bit_off : 0);
+      it.start_bit = c.sp[s].in_off * 8 + (s == 0 ? c.bit_off : 0);
       it.limit_bit = ~0ull;
-      it.end_byte = S.in_off + S.in_len;
+      it.end_byte = c.sp[s].in_off + c.sp[s].in_len;
       it.stream = (uint32_t)s;
-      it.flags = ((uint32_t)format << ITEM_FMT_SHIFT) | ITEM_HEAD | ((s == 0 && resume_abs) ? ITEM_RESUME : 0u);
-      items.push_back(it);
-      S.first_item = (uint32_t)s;
-      S.first_marker = 0;
-      S.n_items = 1;
-      S.cur_item = S.first_item;
+      it.flags = ((uint32_t)c.format << ITEM_FMT_SHIFT) | ITEM_HEAD | ((s == 0 && c.resume_abs) ? ITEM_RESUME : 0u);
+      c.items.push_back(it);
     }
-    if ((r = upload(ctx, ctx->d_items, items))) return r;
-    host_tables = true;
+    if ((r = upload(ctx, ctx->d_items, c.items))) return r;
   }
-  // ---------------------------------------------------------------- K0b: speculative block starts
-  // Streams whose items are large (few or no flush markers: ordinary zlib / gzip output) are searched for plausible
-  // dynamic-Huffman block headers; the candidates join the markers (one ascending list of bit positions per stream)
-  // and the items are built again from the merged list.  Nothing downstream tells a candidate from a marker.
-  const u64* d_markers_cur = (const u64*)ctx->d_markers.p;
-  const u32* d_first_marker = (const u32*)ctx->d_k0_fm.p + 2;
-  if (tiles && ctx->find_mode) {
-    constexpr uint64_t FIND_MIN_ITEM_BITS = 8ull * (48u << 10);  // mean compressed octets per item below which it does not pay
-    // ... nor when the call already has enough items to fill the chip (a batch of thousands of streams: measured on
-    // config 3, 4096 gzip members, splitting them cost more in K2's second plane than it gained in K1)
-    // ... nor when every stream begins with a stored block (stored data: nothing to find; config 1)
-    const bool enough = (size_t)n_mark + n >= (size_t)ctx->tun.find_enough || (n_stored_heads >= n && ctx->find_mode != 2);
-    const uint64_t find_min_len = (uint64_t)ctx->tun.find_min_len;
-    std::vector<uint32_t> tfb(n + 1);
-    uint64_t tiles_b = 0;
-    for (size_t s = 0; s < n; s++) {
-      tfb[s] = (uint32_t)tiles_b;
-      const uint64_t items_s = 1 + (first_marker[s + 1] - first_marker[s]);
-      const bool search = ctx->find_mode == 2 ? sp[s].in_len >= 64 : (!enough && sp[s].in_len >= find_min_len && sp[s].in_len * 8 / items_s >= FIND_MIN_ITEM_BITS);
-      if (search) tiles_b += ((((uintptr_t)d_in + in_offs[s]) & 15) + in_lens[s] + K0B_TILE - 1) / K0B_TILE;
-      if (tiles_b > 0x7fffffffu) return TBZ_E_ARG;
-    }
-    tfb[n] = (uint32_t)tiles_b;
-    if (tiles_b) {
-      TBZ_HIP(hipEventRecord(ctx->ev[8], ctx->stream));
-      if ((r = upload(ctx, ctx->d_kb_tf, tfb))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_slots, tiles_b * (size_t)K0B_SLOTS * 8))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_counts, tiles_b * 4))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_kcounts, tiles_b * 4))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_keep, tiles_b * (size_t)(K0B_SLOTS / 64) * 8))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_offsets, (tiles_b + 1) * 4))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_cands, tiles_b * (size_t)K0B_SLOTS * 8 + 16))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_fc, (n + 1) * 4))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_head, 16))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_fm2, (n + 1) * 4 + 8))) return r;
-      if ((r = ensure(ctx, ctx->d_markers2, ((size_t)n_mark + tiles_b * (size_t)K0B_SLOTS) * 8 + 16))) return r;
-      K0bParams kb{(const u8*)d_in, (const u64*)ctx->d_str_off.p, (const u64*)ctx->d_str_len.p,
-                   (const u32*)ctx->d_kb_tf.p, (u32)n, (u32)tiles_b, (u64*)ctx->d_kb_slots.p, (u32*)ctx->d_kb_counts.p,
-                   (u32*)ctx->d_kb_offsets.p, (u64*)ctx->d_kb_cands.p, (u32*)ctx->d_kb_fc.p, (u32*)ctx->d_kb_head.p,
-                   (const u64*)ctx->d_markers.p, (const u32*)ctx->d_k0_fm.p + 2, (u64*)ctx->d_markers2.p,
-                   (u32*)ctx->d_kb_fm2.p + 2, (u32*)ctx->d_kb_fm2.p, bit_off, K0B_SLOTS,
-                   ctx->tun.k0b_pair >= 0 ? (u32)(ctx->tun.k0b_pair != 0) : (tiles_b >= 8192 ? 1u : 0u), nullptr, nullptr,
-                   (u64*)ctx->d_kb_keep.p, (u32*)ctx->d_kb_kcounts.p, 0};
-      TBZ_LAUNCH(tbz_k0b_scan, tiles_b, ctx->stream, kb);
-      // (a launch that fits the chip at once — 64 MiB of input — is as long as its slowest wave: a tile per wave; beyond
-      // that it is throughput that counts: two tiles per wave, 32 lanes each)
-      TBZ_LAUNCH(tbz_k0b_validate, kb.pair ? (tiles_b + 1) / 2 : tiles_b, ctx->stream, kb);
-#ifdef TBZ_WAVE_TRACE
-      if (const char* vp = getenv("TBZ_VAL_TRACE")) {
-        std::vector<u64> h(8192 * 8);
-        hipStreamSynchronize(ctx->stream);
-        hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(tbz_dbg), h.size() * 8);
-        if (FILE* f = fopen(vp, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-      }
-#endif
-      TBZ_LAUNCH(tbz_k0b_space, tiles_b, ctx->stream, kb);  // (candidates too close to a marker, the head or each other: dropped)
-      TBZ_LAUNCH_WG(tbz_k0b_offsets, 1, K0B_SCAN_THREADS, ctx->stream, kb);
-      TBZ_LAUNCH(tbz_k0b_compact, tiles_b, ctx->stream, kb);
-      const size_t max_merge = (size_t)n_mark + tiles_b * (size_t)K0B_SLOTS;
-      TBZ_LAUNCH(tbz_k0b_merge, (max_merge + 63) / 64, ctx->stream, kb);
-      uint32_t* h_head = (uint32_t*)ctx->h_pin;
-      TBZ_HIP(hipMemcpyAsync(h_head, ctx->d_kb_fm2.p, (n + 3) * 4, hipMemcpyDeviceToHost, ctx->stream));
-      TBZ_HIP(hipStreamSynchronize(ctx->stream));
-      const uint32_t n_merged = h_head[0];
-      ctx->tim.n_candidates = n_merged - n_mark;
-      if (const char* dp = ctx->tun.debug_cands.empty() ? nullptr : ctx->tun.debug_cands.c_str()) {  // the merged list of bit positions, for tools/ that compare it with the true block starts
-        std::vector<uint64_t> hm(n_merged);
-        TBZ_HIP(hipMemcpy(hm.data(), ctx->d_markers2.p, hm.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(dp, "wb")) {
-          fwrite(hm.data(), 8, hm.size(), f);
-          fclose(f);
-        }
-      }
-      if (n_merged != n_mark) {
-        n_mark = n_merged;
-        for (size_t s = 0; s <= n; s++) first_marker[s] = h_head[2 + s];
-        if ((r = ensure(ctx, ctx->d_items, ((size_t)n_mark + n) * sizeof(Item)))) return r;
-        K0Params k0m{};
-        k0m.str_off = (const u64*)ctx->d_str_off.p;
-        k0m.str_len = (const u64*)ctx->d_str_len.p;
-        k0m.n_streams = (u32)n;
-        k0m.markers = (u64*)ctx->d_markers2.p;
-        k0m.first_marker = (u32*)ctx->d_kb_fm2.p + 2;
-        k0m.head = (u32*)ctx->d_kb_fm2.p;
-        k0m.items = (Item*)ctx->d_items.p;
-        k0m.format = (u32)format;
-        k0m.second_pass = 1;
-        k0m.start_bit_off = bit_off;
-        k0m.resume = resume_abs ? 1u : 0u;
-        TBZ_LAUNCH(tbz_k0_items, ((size_t)n_mark + n + 63) / 64, ctx->stream, k0m);
-        d_markers_cur = (const u64*)ctx->d_markers2.p;
-        d_first_marker = (const u32*)ctx->d_kb_fm2.p + 2;
-        for (size_t s = 0; s < n; s++) {
-          StreamPlan& S = sp[s];
-          S.first_marker = first_marker[s];
-          S.first_item = first_marker[s] + (uint32_t)s;
-          S.n_items = 1 + (first_marker[s + 1] - first_marker[s]);
-          S.cur_item = S.first_item;
-        }
-      }
-      TBZ_HIP(hipGetLastError());
-      TBZ_HIP(hipEventRecord(ctx->ev[9], ctx->stream));
-      have_find = true;
+  set_item_ranges(c);
+  c.d_markers_cur = (const u64*)ctx->d_markers.p;
+  c.d_first_marker = (const u32*)ctx->d_k0_fm.p + 2;
+  return 0;
+}
+// K0b / K0c: the search tiles (`tile` octets) of the streams that are searched — all of at least 64 octets under
+// TBZ_FIND=always; else, unless the call has `enough` items, those of at least min_len octets whose items average
+// min_item_bits or more.  When there are any, event 8 (the search's start) and the tile table (to `tf_buf`) follow.
+static int search_tiles(Call& c, uint64_t tile, bool enough, uint64_t min_len, uint64_t min_item_bits, DevBuf& tf_buf,
+                        uint64_t* n_tiles) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
+  std::vector<uint32_t> tf(n + 1);
+  uint64_t t = 0;
+  for (size_t s = 0; s < n; s++) {
+    tf[s] = (uint32_t)t;
+    const uint64_t items_s = 1 + (c.first_marker[s + 1] - c.first_marker[s]);
+    const uint64_t len = c.sp[s].in_len;
+    const bool search = ctx->find_mode == 2 ? len >= 64 : (!enough && len >= min_len && len * 8 / items_s >= min_item_bits);
+    if (search) t += ((((uintptr_t)c.d_in + c.in_offs[s]) & 15) + c.in_lens[s] + tile - 1) / tile;
+    if (t > 0x7fffffffu) return TBZ_E_ARG;
+  }
+  tf[n] = (uint32_t)t;
+  *n_tiles = t;
+  if (!t) return 0;
+  int r;
+  if (!c.have_find && (r = record(ctx, 8))) return r;
+  return upload(ctx, tf_buf, tf);
+}
+// K0b / K0c: the buffers both searches use, for `tiles` search tiles of `slots` candidate slots each (cand_slots: the
+// search's own slot array), and the parameters they share; the merged list goes to `markers`, its head and per-stream
+// starts to `fm2`.  (pair, ends, link and max_block are the caller's.)
+static int search_setup(Call& c, uint64_t tiles, u32 slots, DevBuf& tf, DevBuf& cand_slots, DevBuf& fm2, DevBuf& markers,
+                        K0bParams& kb) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n, nslot = tiles * (size_t)slots;
+  int r;
+  if ((r = ensure(ctx, cand_slots, nslot * 8))) return r;
+  if ((r = ensure(ctx, ctx->d_kb_counts, tiles * 4))) return r;
+  if ((r = ensure(ctx, ctx->d_kb_kcounts, tiles * 4))) return r;
+  if ((r = ensure(ctx, ctx->d_kb_keep, tiles * (size_t)(slots / 64) * 8))) return r;
+  if ((r = ensure(ctx, ctx->d_kb_offsets, (tiles + 1) * 4))) return r;
+  if ((r = ensure(ctx, ctx->d_kb_cands, nslot * 8 + 16))) return r;
+  if ((r = ensure(ctx, ctx->d_kb_fc, (n + 1) * 4))) return r;
+  if ((r = ensure(ctx, ctx->d_kb_head, 16))) return r;
+  if ((r = ensure(ctx, fm2, (n + 1) * 4 + 8))) return r;
+  if ((r = ensure(ctx, markers, ((size_t)c.n_mark + nslot) * 8 + 16))) return r;
+  kb = K0bParams{(const u8*)c.d_in, (const u64*)ctx->d_str_off.p, (const u64*)ctx->d_str_len.p,
+                 (const u32*)tf.p, (u32)n, (u32)tiles, (u64*)cand_slots.p, (u32*)ctx->d_kb_counts.p,
+                 (u32*)ctx->d_kb_offsets.p, (u64*)ctx->d_kb_cands.p, (u32*)ctx->d_kb_fc.p, (u32*)ctx->d_kb_head.p,
+                 c.d_markers_cur, c.d_first_marker, (u64*)markers.p,
+                 (u32*)fm2.p + 2, (u32*)fm2.p, c.bit_off, slots, 0, nullptr, nullptr,
+                 (u64*)ctx->d_kb_keep.p, (u32*)ctx->d_kb_kcounts.p, 0};
+  return 0;
+}
+// K0b / K0c once the candidates that stay are marked: compacted and merged with the markers (into search_setup's
+// `markers` and `fm2`), the merged list's head read back.  When candidates joined the markers, the items are built
+// again from the merged list.  dump: K0b's list goes to TBZ_DEBUG_CANDS.
+static int merge_candidates(Call& c, const K0bParams& kb, DevBuf& markers, DevBuf& fm2, bool dump) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
+  int r;
+  TBZ_LAUNCH_WG(tbz_k0b_offsets, 1, K0B_SCAN_THREADS, ctx->stream, kb);
+  TBZ_LAUNCH(tbz_k0b_compact, kb.n_tiles, ctx->stream, kb);
+  const size_t max_merge = (size_t)c.n_mark + kb.n_tiles * (size_t)kb.slots_per_tile;
+  TBZ_LAUNCH(tbz_k0b_merge, (max_merge + 63) / 64, ctx->stream, kb);
+  uint32_t* h_head = (uint32_t*)ctx->h_pin;
+  if ((r = read_back(ctx, h_head, fm2.p, (n + 3) * 4))) return r;
+  const uint32_t n_merged = h_head[0];
+  ctx->tim.n_candidates += n_merged - c.n_mark;
+  if (const char* dp = (!dump || ctx->tun.debug_cands.empty()) ? nullptr : ctx->tun.debug_cands.c_str()) {  // the merged list of bit positions, for tools/ that compare it with the true block starts
+    std::vector<uint64_t> hm(n_merged);
+    TBZ_HIP(hipMemcpy(hm.data(), markers.p, hm.size() * 8, hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(dp, "wb")) {
+      fwrite(hm.data(), 8, hm.size(), f);
+      fclose(f);
     }
   }
-  // ---------------------------------------------------------------- K0c: chains of fixed-Huffman blocks
-  // Streams whose items are STILL large (K0 and K0b found little in them: fixed-Huffman or stored territory) are
-  // searched for "end-of-block + BTYPE 1" patterns; each hit's one block is skimmed and the hits that chain are kept.
-  if (tiles && ctx->find_mode) {
-    constexpr uint64_t FIXED_MIN_ITEM_BITS = 8ull * (256u << 10);
-    // flush-delimited items that begin with fixed-Huffman blocks (K0 counted them) are chains of such blocks, and a
-    // periodic bitstream — what fixed-Huffman territory tends to be — never lets K1's lanes fall into step: block starts
-    // are what makes such items parallel, so they are searched from 32 Kbit per item on
-    const bool fixed_territory = n_fixed_items != 0 && 2 * (uint64_t)n_fixed_items >= n_mark;
-    const uint64_t min_item_bits = fixed_territory ? 32u << 10 : FIXED_MIN_ITEM_BITS;
-    std::vector<uint32_t> tfc(n + 1);
-    uint64_t tiles_c = 0;
-    const bool enough = (size_t)n_mark + n >= 2048;
-    for (size_t s = 0; s < n; s++) {
-      tfc[s] = (uint32_t)tiles_c;
-      const uint64_t items_s = 1 + (first_marker[s + 1] - first_marker[s]);
-      const bool search = ctx->find_mode == 2 ? sp[s].in_len >= 64
-                                              : (!enough && sp[s].in_len * 8 / items_s >= min_item_bits);
-      if (search) tiles_c += ((((uintptr_t)d_in + in_offs[s]) & 15) + in_lens[s] + K0C_TILE - 1) / K0C_TILE;
-      if (tiles_c > 0x7fffffffu) return TBZ_E_ARG;
-    }
-    tfc[n] = (uint32_t)tiles_c;
-    if (tiles_c) {
-      if (!have_find) TBZ_HIP(hipEventRecord(ctx->ev[8], ctx->stream));
-      const size_t nslot = tiles_c * (size_t)K0C_SLOTS;
-      if ((r = upload(ctx, ctx->d_kc_tf, tfc))) return r;
-      if ((r = ensure(ctx, ctx->d_kc_slots, nslot * 8))) return r;
-      if ((r = ensure(ctx, ctx->d_kc_ends, nslot * 8))) return r;
-      if ((r = ensure(ctx, ctx->d_kc_link, nslot * 2))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_counts, tiles_c * 4))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_kcounts, tiles_c * 4))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_keep, tiles_c * (size_t)(K0C_SLOTS / 64) * 8))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_offsets, (tiles_c + 1) * 4))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_cands, nslot * 8 + 16))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_fc, (n + 1) * 4))) return r;
-      if ((r = ensure(ctx, ctx->d_kb_head, 16))) return r;
-      if ((r = ensure(ctx, ctx->d_kc_fm2, (n + 1) * 4 + 8))) return r;
-      if ((r = ensure(ctx, ctx->d_markers3, ((size_t)n_mark + nslot) * 8 + 16))) return r;
-      TBZ_HIP(hipMemsetAsync(ctx->d_kc_link.p, 0, nslot * 2, ctx->stream));
-      K0bParams kc{(const u8*)d_in, (const u64*)ctx->d_str_off.p, (const u64*)ctx->d_str_len.p,
-                   (const u32*)ctx->d_kc_tf.p, (u32)n, (u32)tiles_c, (u64*)ctx->d_kc_slots.p, (u32*)ctx->d_kb_counts.p,
-                   (u32*)ctx->d_kb_offsets.p, (u64*)ctx->d_kb_cands.p, (u32*)ctx->d_kb_fc.p, (u32*)ctx->d_kb_head.p,
-                   d_markers_cur, d_first_marker, (u64*)ctx->d_markers3.p,
-                   (u32*)ctx->d_kc_fm2.p + 2, (u32*)ctx->d_kc_fm2.p, bit_off, K0C_SLOTS, 0, (u64*)ctx->d_kc_ends.p,
-                   (u8*)ctx->d_kc_link.p, (u64*)ctx->d_kb_keep.p, (u32*)ctx->d_kb_kcounts.p,
-                   ctx->tun.k0c_max_block ? (u64)ctx->tun.k0c_max_block : K0C_MAX_BLOCK};
-      TBZ_LAUNCH(tbz_k0c_scan, tiles_c, ctx->stream, kc);
-      TBZ_LAUNCH(tbz_k0c_skim, tiles_c * (size_t)(K0C_SLOTS / 64), ctx->stream, kc);
-      TBZ_LAUNCH(tbz_k0c_link, tiles_c, ctx->stream, kc);
-      TBZ_LAUNCH(tbz_k0c_filter, tiles_c, ctx->stream, kc);
-      TBZ_LAUNCH_WG(tbz_k0b_offsets, 1, K0B_SCAN_THREADS, ctx->stream, kc);
-      TBZ_LAUNCH(tbz_k0b_compact, tiles_c, ctx->stream, kc);
-      const size_t max_merge = (size_t)n_mark + nslot;
-      TBZ_LAUNCH(tbz_k0b_merge, (max_merge + 63) / 64, ctx->stream, kc);
-      uint32_t* h_head = (uint32_t*)ctx->h_pin;
-      TBZ_HIP(hipMemcpyAsync(h_head, ctx->d_kc_fm2.p, (n + 3) * 4, hipMemcpyDeviceToHost, ctx->stream));
-      TBZ_HIP(hipStreamSynchronize(ctx->stream));
-      const uint32_t n_merged = h_head[0];
-      ctx->tim.n_candidates += n_merged - n_mark;
-      if (n_merged != n_mark) {
-        n_mark = n_merged;
-        for (size_t s = 0; s <= n; s++) first_marker[s] = h_head[2 + s];
-        if ((r = ensure(ctx, ctx->d_items, ((size_t)n_mark + n) * sizeof(Item)))) return r;
-        K0Params k0m{};
-        k0m.str_off = (const u64*)ctx->d_str_off.p;
-        k0m.str_len = (const u64*)ctx->d_str_len.p;
-        k0m.n_streams = (u32)n;
-        k0m.markers = (u64*)ctx->d_markers3.p;
-        k0m.first_marker = (u32*)ctx->d_kc_fm2.p + 2;
-        k0m.head = (u32*)ctx->d_kc_fm2.p;
-        k0m.items = (Item*)ctx->d_items.p;
-        k0m.format = (u32)format;
-        k0m.second_pass = 1;
-        k0m.start_bit_off = bit_off;
-        k0m.resume = resume_abs ? 1u : 0u;
-        TBZ_LAUNCH(tbz_k0_items, ((size_t)n_mark + n + 63) / 64, ctx->stream, k0m);
-        d_markers_cur = (const u64*)ctx->d_markers3.p;
-        d_first_marker = (const u32*)ctx->d_kc_fm2.p + 2;
-        for (size_t s = 0; s < n; s++) {
-          StreamPlan& S = sp[s];
-          S.first_marker = first_marker[s];
-          S.first_item = first_marker[s] + (uint32_t)s;
-          S.n_items = 1 + (first_marker[s + 1] - first_marker[s]);
-          S.cur_item = S.first_item;
-        }
-      }
-      TBZ_HIP(hipGetLastError());
-      TBZ_HIP(hipEventRecord(ctx->ev[9], ctx->stream));
-      have_find = true;
-    }
+  if (n_merged != c.n_mark) {
+    c.n_mark = n_merged;
+    for (size_t s = 0; s <= n; s++) c.first_marker[s] = h_head[2 + s];
+    if ((r = ensure(ctx, ctx->d_items, ((size_t)c.n_mark + n) * sizeof(Item)))) return r;
+    K0Params k0m{};
+    k0m.str_off = (const u64*)ctx->d_str_off.p;
+    k0m.str_len = (const u64*)ctx->d_str_len.p;
+    k0m.n_streams = (u32)n;
+    k0m.markers = (u64*)markers.p;
+    k0m.first_marker = (u32*)fm2.p + 2;
+    k0m.head = (u32*)fm2.p;
+    k0m.items = (Item*)ctx->d_items.p;
+    k0m.format = (u32)c.format;
+    k0m.second_pass = 1;
+    k0m.start_bit_off = c.bit_off;
+    k0m.resume = c.resume_abs ? 1u : 0u;
+    TBZ_LAUNCH(tbz_k0_items, ((size_t)c.n_mark + n + 63) / 64, ctx->stream, k0m);
+    c.d_markers_cur = (const u64*)markers.p;
+    c.d_first_marker = (const u32*)fm2.p + 2;
+    set_item_ranges(c);
   }
-  const size_t n_items = (size_t)n_mark + n;
-  auto fetch_host_tables = [&]() -> int {  // the general layout path walks the items on the host
-    if (host_tables) return 0;
-    items.resize(n_items);
-    TBZ_HIP(hipMemcpyAsync(items.data(), ctx->d_items.p, n_items * sizeof(Item), hipMemcpyDeviceToHost, ctx->stream));
-    TBZ_HIP(hipStreamSynchronize(ctx->stream));
-    host_tables = true;
-    return 0;
-  };
-  if ((r = record(ctx, 1))) return r;
+  TBZ_HIP(hipGetLastError());
+  TBZ_HIP(hipEventRecord(ctx->ev[9], ctx->stream));
+  c.have_find = true;
+  return 0;
+}
 
-  // token pool: one u16 per TWO input bits where gangs decode (a token of ordinary data takes eight bits and more; a
-  // lane whose region fills up ends its run early and an item that does not fit is declined — SEG_REDO — and decoded
-  // again by one lane into a region of its own: `dense`), one per bit where the one-lane kernel does (K1 never writes
-  // more words than bits consumed); run tables: one 16-octet slot per 2^RUN_SHIFT input bits.  Both are addressed by
-  // bit position RELATIVE to the first stream octet of the call (pool_base: a batch that is a window into a large
-  // buffer pays for its own extent only); the repair launches' pools cover the repaired streams' tails only (pool2_base).
-  if (in_lo > in_extent) in_lo = in_extent;
-  const uint64_t pool_base = (in_lo * 8) & ~(uint64_t)((1u << RUN_SHIFT) - 1);  // bits
-  const uint64_t pool_bits = in_extent * 8 - pool_base;
-  uint64_t pool2_base = pool_base, pool2_hi = 0;
-  u32 half1 = 0, half2 = 0;  // log2 of the input bits per token word of the call's pool / the repair pool
+// ---------------------------------------------------------------- K0b: speculative block starts
+// Streams whose items are large (few or no flush markers: ordinary zlib / gzip output) are searched for plausible
+// dynamic-Huffman block headers; the candidates join the markers (one ascending list of bit positions per stream)
+// and the items are built again from the merged list.  Nothing downstream tells a candidate from a marker.
+static int call_k0b(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  if (!c.tiles || !ctx->find_mode) return 0;
+  constexpr uint64_t FIND_MIN_ITEM_BITS = 8ull * (48u << 10);  // mean compressed octets per item below which it does not pay
+  // ... nor when the call already has enough items to fill the chip (a batch of thousands of streams: measured on
+  // config 3, 4096 gzip members, splitting them cost more in K2's second plane than it gained in K1)
+  // ... nor when every stream begins with a stored block (stored data: nothing to find; config 1)
+  const bool enough = (size_t)c.n_mark + c.n >= (size_t)ctx->tun.find_enough || (c.n_stored_heads >= c.n && ctx->find_mode != 2);
+  uint64_t tiles_b = 0;
+  int r;
+  if ((r = search_tiles(c, K0B_TILE, enough, (uint64_t)ctx->tun.find_min_len, FIND_MIN_ITEM_BITS, ctx->d_kb_tf, &tiles_b))) return r;
+  if (!tiles_b) return 0;
+  K0bParams kb;
+  if ((r = search_setup(c, tiles_b, K0B_SLOTS, ctx->d_kb_tf, ctx->d_kb_slots, ctx->d_kb_fm2, ctx->d_markers2, kb))) return r;
+  kb.pair = ctx->tun.k0b_pair >= 0 ? (u32)(ctx->tun.k0b_pair != 0) : (tiles_b >= 8192 ? 1u : 0u);
+  TBZ_LAUNCH(tbz_k0b_scan, tiles_b, ctx->stream, kb);
+  // (a launch that fits the chip at once — 64 MiB of input — is as long as its slowest wave: a tile per wave; beyond
+  // that it is throughput that counts: two tiles per wave, 32 lanes each)
+  TBZ_LAUNCH(tbz_k0b_validate, kb.pair ? (tiles_b + 1) / 2 : tiles_b, ctx->stream, kb);
+#ifdef TBZ_WAVE_TRACE
+  if (const char* vp = getenv("TBZ_VAL_TRACE")) {
+    std::vector<u64> h(8192 * 8);
+    hipStreamSynchronize(ctx->stream);
+    hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(tbz_dbg), h.size() * 8);
+    if (FILE* f = fopen(vp, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+  }
+#endif
+  TBZ_LAUNCH(tbz_k0b_space, tiles_b, ctx->stream, kb);  // (candidates too close to a marker, the head or each other: dropped)
+  return merge_candidates(c, kb, ctx->d_markers2, ctx->d_kb_fm2, true);
+}
+
+// ---------------------------------------------------------------- K0c: chains of fixed-Huffman blocks
+// Streams whose items are STILL large (K0 and K0b found little in them: fixed-Huffman or stored territory) are
+// searched for "end-of-block + BTYPE 1" patterns; each hit's one block is skimmed and the hits that chain are kept.
+static int call_k0c(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  if (!c.tiles || !ctx->find_mode) return 0;
+  constexpr uint64_t FIXED_MIN_ITEM_BITS = 8ull * (256u << 10);
+  // flush-delimited items that begin with fixed-Huffman blocks (K0 counted them) are chains of such blocks, and a
+  // periodic bitstream — what fixed-Huffman territory tends to be — never lets K1's lanes fall into step: block starts
+  // are what makes such items parallel, so they are searched from 32 Kbit per item on
+  const bool fixed_territory = c.n_fixed_items != 0 && 2 * (uint64_t)c.n_fixed_items >= c.n_mark;
+  const uint64_t min_item_bits = fixed_territory ? 32u << 10 : FIXED_MIN_ITEM_BITS;
+  const bool enough = (size_t)c.n_mark + c.n >= 2048;
+  uint64_t tiles_c = 0;
+  int r;
+  if ((r = search_tiles(c, K0C_TILE, enough, 0, min_item_bits, ctx->d_kc_tf, &tiles_c))) return r;
+  if (!tiles_c) return 0;
+  const size_t nslot = tiles_c * (size_t)K0C_SLOTS;
+  K0bParams kc;
+  if ((r = search_setup(c, tiles_c, K0C_SLOTS, ctx->d_kc_tf, ctx->d_kc_slots, ctx->d_kc_fm2, ctx->d_markers3, kc))) return r;
+  if ((r = ensure(ctx, ctx->d_kc_ends, nslot * 8))) return r;
+  if ((r = ensure(ctx, ctx->d_kc_link, nslot * 2))) return r;
+  TBZ_HIP(hipMemsetAsync(ctx->d_kc_link.p, 0, nslot * 2, ctx->stream));
+  kc.ends = (u64*)ctx->d_kc_ends.p;
+  kc.link = (u8*)ctx->d_kc_link.p;
+  kc.max_block = ctx->tun.k0c_max_block ? (u64)ctx->tun.k0c_max_block : K0C_MAX_BLOCK;
+  TBZ_LAUNCH(tbz_k0c_scan, tiles_c, ctx->stream, kc);
+  TBZ_LAUNCH(tbz_k0c_skim, tiles_c * (size_t)(K0C_SLOTS / 64), ctx->stream, kc);
+  TBZ_LAUNCH(tbz_k0c_link, tiles_c, ctx->stream, kc);
+  TBZ_LAUNCH(tbz_k0c_filter, tiles_c, ctx->stream, kc);
+  return merge_candidates(c, kc, ctx->d_markers3, ctx->d_kc_fm2, false);
+}
+
+// ---------------------------------------------------------------- K1: flavour, pools, launches
+// K1 flavour.  One lane per item is bound by ONE item's serial chain (~1.1 us per token) and decodes
+// without lookup tables; a gang of G lanes shares one item and one set of LDS tables.  G follows the
+// average item size (a lane should get at least ~2 Kibit of bitstream per round); only batches of
+// many tiny items (table set-up would dominate) stay with one lane per item.
+static int k1_gang(const Call& c, size_t n_it) {
+  if (c.ctx->k1_mode) return c.ctx->k1_mode;
+  uint64_t avg_bits = n_it ? c.in_total_bits / n_it : 0;
+  if (avg_bits < 8192 && n_it >= 16384) return 1;
+  int G = 8;
+  while (G < 64 && avg_bits > (uint64_t)G * 3072) G <<= 1;
+  return G;
+}
+// a token pool and its run tables for `bits` input bits, at the density the K1 flavour for n_it items needs
+static int size_pool(Call& c, size_t n_it, uint64_t bits, DevBuf& tok, DevBuf& runs, u32& half) {
+  half = (k1_gang(c, n_it) == 1 || c.ctx->tun.tok_full) ? 0u : 1u;
+  int r = ensure(c.ctx, tok, ((size_t)bits >> half) * 2 + 256);
+  return r ? r : ensure(c.ctx, runs, ((size_t)bits >> RUN_SHIFT) * sizeof(RunRec) + 1024);
+}
+// token pool: one u16 per TWO input bits where gangs decode (a token of ordinary data takes eight bits and more; a
+// lane whose region fills up ends its run early and an item that does not fit is declined — SEG_REDO — and decoded
+// again by one lane into a region of its own: `dense`), one per bit where the one-lane kernel does (K1 never writes
+// more words than bits consumed); run tables: one 16-octet slot per 2^RUN_SHIFT input bits.  Both are addressed by
+// bit position RELATIVE to the first stream octet of the call (pool_base: a batch that is a window into a large
+// buffer pays for its own extent only); the repair launches' pools cover the repaired streams' tails only (pool2_base).
+static int call_pools(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  int r;
+  c.n_items = (size_t)c.n_mark + c.n;
+  if ((r = record(ctx, 1))) return r;
+  if (c.in_lo > c.in_extent) c.in_lo = c.in_extent;
+  c.pool_base = (c.in_lo * 8) & ~(uint64_t)((1u << RUN_SHIFT) - 1);  // bits
+  const uint64_t pool_bits = c.in_extent * 8 - c.pool_base;
   if (!ctx->dense.empty()) {  // (the last call's; rare)
     for (DevBuf& b : ctx->dense)
       if (b.p) hipFree(b.p);
     ctx->dense.clear();
   }
-  if ((r = ensure(ctx, ctx->d_res, n_items * sizeof(SegResult)))) return r;
-  // K1 flavour.  One lane per item is bound by ONE item's serial chain (~1.1 us per token) and decodes
-  // without lookup tables; a gang of G lanes shares one item and one set of LDS tables.  G follows the
-  // average item size (a lane should get at least ~2 Kibit of bitstream per round); only batches of
-  // many tiny items (table set-up would dominate) stay with one lane per item.
-  auto k1_gang = [&](size_t n_it) -> int {
-    if (ctx->k1_mode) return ctx->k1_mode;
-    uint64_t avg_bits = n_it ? in_total_bits / n_it : 0;
-    if (avg_bits < 8192 && n_it >= 16384) return 1;
-    int G = 8;
-    while (G < 64 && avg_bits > (uint64_t)G * 3072) G <<= 1;
-    return G;
-  };
-  half1 = (k1_gang(n_items) == 1 || ctx->tun.tok_full) ? 0u : 1u;
-  if ((r = ensure(ctx, ctx->d_tok, ((size_t)pool_bits >> half1) * 2 + 256))) return r;
-  if ((r = ensure(ctx, ctx->d_runs, ((size_t)pool_bits >> RUN_SHIFT) * sizeof(RunRec) + 1024))) return r;
-  // regions of their own for items that are decoded again: one word per bit of each item, and a run table
-  auto make_explicit = [&](std::vector<Item>& its) -> int {
-    uint64_t words = 0, slots = 0;
-    std::vector<uint64_t> at(its.size()), rat(its.size());
-    for (size_t k = 0; k < its.size(); k++) {
-      const Item& q = its[k];
-      const uint64_t hi = (q.flags & ITEM_FIXUP) ? q.end_byte * 8 : std::min(q.limit_bit, q.end_byte * 8);
-      const uint64_t span = hi > q.start_bit ? hi - q.start_bit : 0;
-      at[k] = words;
-      rat[k] = slots;
-      words += (span + 64 + 7) & ~7ull;
-      slots += (span >> RUN_SHIFT) + 2;
-    }
-    ctx->dense.emplace_back();
-    int rr = ensure(ctx, ctx->dense.back(), (size_t)words * 2 + (size_t)slots * sizeof(RunRec) + 256);
-    if (rr) return rr;
-    u16* tk = (u16*)ctx->dense.back().p;
-    RunRec* rn = (RunRec*)(tk + words);  // (words is a multiple of 8: 16-octet aligned)
-    for (size_t k = 0; k < its.size(); k++) {
-      its[k].flags |= ITEM_EXPLICIT;
-      its[k].tok = (uint64_t)(tk + at[k]);
-      its[k].runs = (uint64_t)(rn + rat[k]);
-    }
-    return 0;
-  };
-  auto items_per_wg = [](size_t n_it) {  // lane-per-item flavour: spread few items over all CUs
-    u32 ipw = 64;
-    while (ipw > 1 && n_it / ipw < 512) ipw >>= 1;
-    return ipw;
-  };
-  // Repair (fix-up) launches decode into pools of their own: a gang that repairs an item runs past the marker
-  // it will land on, into the bit range of items whose tokens (position-addressed!) are already in place.
-  // (kernels index the pools by absolute bit position: the pointers handed to them are shifted down by the pool's base)
-  auto pool_half = [&](bool fix) { return fix ? half2 : half1; };
-  auto pool_tok = [&](bool fix) {
-    return fix ? (u16*)ctx->d_tok2.p - ((pool2_base >> half2) & ~7ull) : (u16*)ctx->d_tok.p - ((pool_base >> half1) & ~7ull);
-  };
-  auto pool_runs = [&](bool fix) {
-    return fix ? (RunRec*)ctx->d_runs2.p - (pool2_base >> RUN_SHIFT) : (RunRec*)ctx->d_runs.p - (pool_base >> RUN_SHIFT);
-  };
-  // (the one-lane kernel writes one word per bit at most: its items live in a pool of that density, or bring their own regions)
-  auto launch_lane = [&](const Item* d_items, SegResult* d_res, size_t n_it, bool fix, bool explicit_items = false) -> int {
-    if (pool_half(fix) && !explicit_items) return TBZ_E_INTERNAL;
-    int rr = ensure(ctx, ctx->d_scratch, n_it * (size_t)K1_SCRATCH);
-    if (rr) return rr;
-    K1Params k1{(const u8*)d_in, pool_tok(fix), d_items, d_res, d_markers_cur,
-                (u8*)ctx->d_scratch.p, pool_runs(fix), d_first_marker, (u32)n_mark, (u32)n_it, items_per_wg(n_it), resume_abs};
-    TBZ_LAUNCH(tbz_k1_huff_decode, (n_it + k1.items_per_wg - 1) / k1.items_per_wg, ctx->stream, k1);
-    return 0;
-  };
-  auto sub_min_for = [&](int) -> u32 {
-    if (ctx->tun.sub_min) return (u32)std::max(64, ctx->tun.sub_min & ~63);
-    return KG_SUB_MIN;
-  };
-  // a gang narrower than 64 lanes declines items it would need more than two full rounds for (the width follows the
-  // launch's mean item size: a batch of many small streams and one large one, or K0c's short items and one long block
-  // among them); the host decodes those with gangs of 64 (`redo`).  (Eight rounds until late in round 3: config 5's
-  // 294 Kbit block of one repeated match stayed on its 8-lane gang for 2.4 ms while the rest of the launch was done
-  // after 0.8 — a wider gang had been WORSE there as long as lanes could not fall into step on a periodic bitstream;
-  // with kg_periodic they start on a token.)  Forced flavours (tests) keep everything.
-  auto wide_for = [&](int G, bool fix) -> u64 {
-    if (ctx->tun.wide_bits >= 0) return (u64)ctx->tun.wide_bits;
-    if (ctx->k1_mode || fix || G >= 64) return 0;
-    return (u64)G * KG_SUB_MAX * 2;
-  };
-  auto ovl_for = [&](int G) -> u32 {
-    if (ctx->tun.ovl) return (u32)std::max(64, ctx->tun.ovl);
-    // measured (profiles/README.md): a gang of 64 commits 29 lanes per round at 512 bits of run-up, 59 at 1024 (K1 on
-    // the 64 MiB no-flush stream 2.78 -> 1.56 ms, on config 3 8.96 -> 6.05 ms).  Gangs of 32: config 2's text is flat
-    // from 512 to 1024 bits (2.56 - 2.68 ms), but a sync-flush stream — more and longer matches, because history
-    // reaches across the flush points, so two parses take longer to fall into step — needed 3.2 rounds per item at 512
-    // bits (K1 on config 2b 1.28 ms; 0.95 at 768, 0.80 at 1024).  Narrow gangs (K0c's short items, config 5): 768 is best.
-    return G >= 32 ? 1024u : 768u;
-  };
-  // items the gang kernel declined (SEG_REDO: more token words than the pool has for their bits — long runs of one
-  // octet code that way —, run table full) are decoded again into regions of their own: by gangs of 64 where the pool
-  // holds one word per two bits, and what those decline, or all of them, by the one-lane kernel, which writes one
-  // contiguous run
-  auto redo = [&](const std::vector<Item>& its, std::vector<SegResult>& rs, bool fix) -> int {
-    {  // items a narrow gang handed back (SEG_WIDE): gangs of 64, the leader parsing the first header itself
-      std::vector<Item> wide;
-      std::vector<size_t> widx;
-      for (size_t i = 0; i < rs.size(); i++)
-        if (rs[i].status == SEG_WIDE) {
-          wide.push_back(its[i]);
-          widx.push_back(i);
-        }
-      if (!wide.empty()) {
-        if (ctx->tun.debug) {
-          uint64_t mx = 0;
-          for (const Item& q : wide) mx = std::max<uint64_t>(mx, std::min(q.limit_bit, q.end_byte * 8) - q.start_bit);
-          fprintf(stderr, "tbz: %zu large item(s) handed to gangs of 64 (the largest: %llu bits)\n", wide.size(), (unsigned long long)mx);
-        }
-        int rr;
-        if ((rr = upload(ctx, ctx->d_redo_items, wide))) return rr;
-        if ((rr = ensure(ctx, ctx->d_redo_res, wide.size() * sizeof(SegResult)))) return rr;
-        if ((rr = ensure(ctx, ctx->d_cold, wide.size() * (size_t)KG_COLD_STRIDE))) return rr;
-        K1gParams kg{(const u8*)d_in, pool_tok(fix), pool_runs(fix), pool_half(fix), 0, (const Item*)ctx->d_redo_items.p,
-                     (SegResult*)ctx->d_redo_res.p, d_markers_cur, d_first_marker, nullptr, nullptr, (u32)n_mark,
-                     (u32)wide.size(), ovl_for(64), sub_min_for(64), 0, resume_abs, (u8*)ctx->d_cold.p};
-#ifdef TBZ_WAVE_TRACE
-        kg.trace = nullptr;
-#endif
-        TBZ_LAUNCH(tbz_k1g64_huff_decode, wide.size(), ctx->stream, kg);
-        std::vector<SegResult> tmp(wide.size());
-        TBZ_HIP(hipMemcpyAsync(tmp.data(), ctx->d_redo_res.p, tmp.size() * sizeof(SegResult), hipMemcpyDeviceToHost,
-                               ctx->stream));
-        TBZ_HIP(hipStreamSynchronize(ctx->stream));
-        for (size_t k = 0; k < widx.size(); k++) rs[widx[k]] = tmp[k];
-        ctx->tim.huff_launches++;
-      }
-    }
+  if ((r = ensure(ctx, ctx->d_res, c.n_items * sizeof(SegResult)))) return r;
+  return size_pool(c, c.n_items, pool_bits, ctx->d_tok, ctx->d_runs, c.half1);
+}
+// regions of their own for items that are decoded again: one word per bit of each item, and a run table
+static int make_explicit(tbz_ctx* ctx, std::vector<Item>& its) {
+  uint64_t words = 0, slots = 0;
+  std::vector<uint64_t> at(its.size()), rat(its.size());
+  for (size_t k = 0; k < its.size(); k++) {
+    const Item& q = its[k];
+    const uint64_t hi = (q.flags & ITEM_FIXUP) ? q.end_byte * 8 : std::min(q.limit_bit, q.end_byte * 8);
+    const uint64_t span = hi > q.start_bit ? hi - q.start_bit : 0;
+    at[k] = words;
+    rat[k] = slots;
+    words += (span + 64 + 7) & ~7ull;
+    slots += (span >> RUN_SHIFT) + 2;
+  }
+  ctx->dense.emplace_back();
+  int rr = ensure(ctx, ctx->dense.back(), (size_t)words * 2 + (size_t)slots * sizeof(RunRec) + 256);
+  if (rr) return rr;
+  u16* tk = (u16*)ctx->dense.back().p;
+  RunRec* rn = (RunRec*)(tk + words);  // (words is a multiple of 8: 16-octet aligned)
+  for (size_t k = 0; k < its.size(); k++) {
+    its[k].flags |= ITEM_EXPLICIT;
+    its[k].tok = (uint64_t)(tk + at[k]);
+    its[k].runs = (uint64_t)(rn + rat[k]);
+  }
+  return 0;
+}
+static u32 items_per_wg(size_t n_it) {  // lane-per-item flavour: spread few items over all CUs
+  u32 ipw = 64;
+  while (ipw > 1 && n_it / ipw < 512) ipw >>= 1;
+  return ipw;
+}
+// Repair (fix-up) launches decode into pools of their own: a gang that repairs an item runs past the marker
+// it will land on, into the bit range of items whose tokens (position-addressed!) are already in place.
+// (kernels index the pools by absolute bit position: the pointers handed to them are shifted down by the pool's base)
+static u32 pool_half(const Call& c, bool fix) { return fix ? c.half2 : c.half1; }
+static u16* pool_tok(const Call& c, bool fix) {
+  return fix ? (u16*)c.ctx->d_tok2.p - ((c.pool2_base >> c.half2) & ~7ull) : (u16*)c.ctx->d_tok.p - ((c.pool_base >> c.half1) & ~7ull);
+}
+static RunRec* pool_runs(const Call& c, bool fix) {
+  return fix ? (RunRec*)c.ctx->d_runs2.p - (c.pool2_base >> RUN_SHIFT) : (RunRec*)c.ctx->d_runs.p - (c.pool_base >> RUN_SHIFT);
+}
+// (the one-lane kernel writes one word per bit at most: its items live in a pool of that density, or bring their own regions)
+static int launch_lane(Call& c, const Item* d_items, SegResult* d_res, size_t n_it, bool fix, bool explicit_items = false) {
+  tbz_ctx* ctx = c.ctx;
+  if (pool_half(c, fix) && !explicit_items) return TBZ_E_INTERNAL;
+  int rr = ensure(ctx, ctx->d_scratch, n_it * (size_t)K1_SCRATCH);
+  if (rr) return rr;
+  K1Params k1{(const u8*)c.d_in, pool_tok(c, fix), d_items, d_res, c.d_markers_cur,
+              (u8*)ctx->d_scratch.p, pool_runs(c, fix), c.d_first_marker, (u32)c.n_mark, (u32)n_it, items_per_wg(n_it), c.resume_abs};
+  TBZ_LAUNCH(tbz_k1_huff_decode, (n_it + k1.items_per_wg - 1) / k1.items_per_wg, ctx->stream, k1);
+  return 0;
+}
+static u32 sub_min(const tbz_ctx* ctx) {
+  if (ctx->tun.sub_min) return (u32)std::max(64, ctx->tun.sub_min & ~63);
+  return KG_SUB_MIN;
+}
+// a gang narrower than 64 lanes declines items it would need more than two full rounds for (the width follows the
+// launch's mean item size: a batch of many small streams and one large one, or K0c's short items and one long block
+// among them); the host decodes those with gangs of 64 (`redo`).  (Eight rounds until late in round 3: config 5's
+// 294 Kbit block of one repeated match stayed on its 8-lane gang for 2.4 ms while the rest of the launch was done
+// after 0.8 — a wider gang had been WORSE there as long as lanes could not fall into step on a periodic bitstream;
+// with kg_periodic they start on a token.)  Forced flavours (tests) keep everything.
+static u64 wide_for(const tbz_ctx* ctx, int G, bool fix) {
+  if (ctx->tun.wide_bits >= 0) return (u64)ctx->tun.wide_bits;
+  if (ctx->k1_mode || fix || G >= 64) return 0;
+  return (u64)G * KG_SUB_MAX * 2;
+}
+static u32 ovl_for(const tbz_ctx* ctx, int G) {
+  if (ctx->tun.ovl) return (u32)std::max(64, ctx->tun.ovl);
+  // measured (profiles/README.md): a gang of 64 commits 29 lanes per round at 512 bits of run-up, 59 at 1024 (K1 on
+  // the 64 MiB no-flush stream 2.78 -> 1.56 ms, on config 3 8.96 -> 6.05 ms).  Gangs of 32: config 2's text is flat
+  // from 512 to 1024 bits (2.56 - 2.68 ms), but a sync-flush stream — more and longer matches, because history
+  // reaches across the flush points, so two parses take longer to fall into step — needed 3.2 rounds per item at 512
+  // bits (K1 on config 2b 1.28 ms; 0.95 at 768, 0.80 at 1024).  Narrow gangs (K0c's short items, config 5): 768 is best.
+  return G >= 32 ? 1024u : 768u;
+}
+// the gang kernels' parameters for n_it items: run-up for gangs of G lanes, no wide items, no K1h records; tokens into
+// the call's pool (fix: the repair pool) or, own, into the items' regions of their own
+static K1gParams k1g_params(const Call& c, const Item* d_items, SegResult* d_res, size_t n_it, int G, bool fix, bool own,
+                            u8* cold) {
+  // (experiment builds: no wave trace either)
+  return K1gParams{(const u8*)c.d_in, own ? nullptr : pool_tok(c, fix), own ? nullptr : pool_runs(c, fix),
+                   own ? 0u : pool_half(c, fix), 0, d_items, d_res, c.d_markers_cur, c.d_first_marker, nullptr, nullptr,
+                   (u32)c.n_mark, (u32)n_it, ovl_for(c.ctx, G), sub_min(c.ctx), 0, c.resume_abs, cold};
+}
+// K1 once more over `its`, on the context's stream, into d_redo_items / d_redo_res, read back into `out`: by gangs of 64
+// in the pools (REDO_GANG) or in regions of their own (REDO_GANG_OWN), or by the one-lane kernel in regions of their
+// own (REDO_LANE)
+enum { REDO_GANG, REDO_GANG_OWN, REDO_LANE };
+static int k1_again(Call& c, std::vector<Item>& its, int how, bool fix, std::vector<SegResult>& out) {
+  tbz_ctx* ctx = c.ctx;
+  int r;
+  if (how != REDO_GANG && (r = make_explicit(ctx, its))) return r;
+  if ((r = upload(ctx, ctx->d_redo_items, its))) return r;
+  if ((r = ensure(ctx, ctx->d_redo_res, its.size() * sizeof(SegResult)))) return r;
+  const Item* d_items = (const Item*)ctx->d_redo_items.p;
+  SegResult* d_res = (SegResult*)ctx->d_redo_res.p;
+  if (how == REDO_LANE) {
+    if ((r = launch_lane(c, d_items, d_res, its.size(), fix, true))) return r;
+  } else {
+    if ((r = ensure(ctx, ctx->d_cold, its.size() * (size_t)KG_COLD_STRIDE))) return r;
+    K1gParams kg = k1g_params(c, d_items, d_res, its.size(), 64, fix, how == REDO_GANG_OWN, (u8*)ctx->d_cold.p);
+    TBZ_LAUNCH(tbz_k1g64_huff_decode, its.size(), ctx->stream, kg);
+  }
+  out.resize(its.size());
+  if ((r = read_back(ctx, out.data(), d_res, out.size() * sizeof(SegResult)))) return r;
+  ctx->tim.huff_launches++;
+  return 0;
+}
+// items a narrow gang handed back (SEG_WIDE) are decoded again by gangs of 64, the leader parsing the first header
+// itself.  Items the gang kernel declined (SEG_REDO: more token words than the pool has for their bits — long runs of
+// one octet code that way —, run table full) are decoded again into regions of their own: by gangs of 64 where the pool
+// holds one word per two bits, and what those decline, or all of them, by the one-lane kernel, which writes one
+// contiguous run
+static int redo(Call& c, const std::vector<Item>& its, std::vector<SegResult>& rs, bool fix) {
+  tbz_ctx* ctx = c.ctx;
+  for (int how : {REDO_GANG, REDO_GANG_OWN, REDO_LANE}) {
+    if (how == REDO_GANG_OWN && (!pool_half(c, fix) || ctx->k1_mode)) continue;
     std::vector<Item> sub;
     std::vector<size_t> idx;
     for (size_t i = 0; i < rs.size(); i++)
-      if (rs[i].status == SEG_REDO) {
+      if (rs[i].status == (how == REDO_GANG ? SEG_WIDE : SEG_REDO)) {
         sub.push_back(its[i]);
         idx.push_back(i);
       }
-    if (sub.empty()) return 0;
-    if (pool_half(fix) && !ctx->k1_mode) {
-      if (ctx->tun.debug) fprintf(stderr, "tbz: %zu item(s) decoded again into regions of their own\n", sub.size());
-      int rr;
-      if ((rr = make_explicit(sub))) return rr;
-      if ((rr = upload(ctx, ctx->d_redo_items, sub))) return rr;
-      if ((rr = ensure(ctx, ctx->d_redo_res, sub.size() * sizeof(SegResult)))) return rr;
-      if ((rr = ensure(ctx, ctx->d_cold, sub.size() * (size_t)KG_COLD_STRIDE))) return rr;
-      K1gParams kg{(const u8*)d_in, nullptr, nullptr, 0, 0, (const Item*)ctx->d_redo_items.p,
-                   (SegResult*)ctx->d_redo_res.p, d_markers_cur, d_first_marker, nullptr, nullptr, (u32)n_mark,
-                   (u32)sub.size(), ovl_for(64), sub_min_for(64), 0, resume_abs, (u8*)ctx->d_cold.p};
-#ifdef TBZ_WAVE_TRACE
-      kg.trace = nullptr;
-#endif
-      TBZ_LAUNCH(tbz_k1g64_huff_decode, sub.size(), ctx->stream, kg);
-      std::vector<SegResult> tmp(sub.size());
-      TBZ_HIP(hipMemcpyAsync(tmp.data(), ctx->d_redo_res.p, tmp.size() * sizeof(SegResult), hipMemcpyDeviceToHost,
-                             ctx->stream));
-      TBZ_HIP(hipStreamSynchronize(ctx->stream));
-      ctx->tim.huff_launches++;
-      std::vector<Item> sub2;
-      std::vector<size_t> idx2;
-      for (size_t k = 0; k < idx.size(); k++) {
-        rs[idx[k]] = tmp[k];
-        if (tmp[k].status == SEG_REDO) {
-          sub2.push_back(its[idx[k]]);
-          idx2.push_back(idx[k]);
-        }
-      }
-      sub.swap(sub2);
-      idx.swap(idx2);
-      if (sub.empty()) return 0;
+    if (sub.empty()) continue;
+    if (ctx->tun.debug && how == REDO_GANG) {
+      uint64_t mx = 0;
+      for (const Item& q : sub) mx = std::max<uint64_t>(mx, std::min(q.limit_bit, q.end_byte * 8) - q.start_bit);
+      fprintf(stderr, "tbz: %zu large item(s) handed to gangs of 64 (the largest: %llu bits)\n", sub.size(), (unsigned long long)mx);
     }
-    if (ctx->tun.debug) fprintf(stderr, "tbz: %zu item(s) redone by the one-lane kernel\n", sub.size());
-    int rr;
-    if ((rr = make_explicit(sub))) return rr;
-    if ((rr = upload(ctx, ctx->d_redo_items, sub))) return rr;
-    if ((rr = ensure(ctx, ctx->d_redo_res, sub.size() * sizeof(SegResult)))) return rr;
-    if ((rr = launch_lane((const Item*)ctx->d_redo_items.p, (SegResult*)ctx->d_redo_res.p, sub.size(), fix, true))) return rr;
-    std::vector<SegResult> tmp(sub.size());
-    TBZ_HIP(hipMemcpyAsync(tmp.data(), ctx->d_redo_res.p, tmp.size() * sizeof(SegResult), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    TBZ_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->tun.debug && how == REDO_GANG_OWN) fprintf(stderr, "tbz: %zu item(s) decoded again into regions of their own\n", sub.size());
+    if (ctx->tun.debug && how == REDO_LANE) fprintf(stderr, "tbz: %zu item(s) redone by the one-lane kernel\n", sub.size());
+    std::vector<SegResult> tmp;
+    int r;
+    if ((r = k1_again(c, sub, how, fix, tmp))) return r;
     for (size_t k = 0; k < idx.size(); k++) rs[idx[k]] = tmp[k];
-    ctx->tim.huff_launches++;
-    return 0;
-  };
-  bool wide_beside = false;  // the main launch's large items were decoded by gangs of 64 on the second stream (d_wide_res)
-  auto launch_k1 = [&](const Item* d_items, SegResult* d_res, size_t n_it, bool fix) -> int {
-    int G = k1_gang(n_it);
-    if (G == 1 && pool_half(fix)) G = 8;  // (a repair launch of many small items into a pool laid out for gangs)
-    if (!fix) ctx->tim.k1_gang = (uint32_t)G;
-    if (G == 1) return launch_lane(d_items, d_res, n_it, fix);
-    size_t per = 64 / G, nwg = (n_it + per - 1) / per;
-    // A launch of NARROW gangs (short items) declines the few items that are far larger than its mean (SEG_WIDE).
-    // Gangs of 64 take exactly those — a second kernel over the same item list on the second stream, every workgroup of
-    // which leaves at once unless its item is such a one — BESIDE the narrow launch instead of after the host has read
-    // its results (config 5: one 294 Kbit block among 3 548 items: 0.77 + 0.8 ms one after the other).  Their results
-    // go to an array of their own (the narrow gang writes SEG_WIDE into the item's record).
-    if (!fix && G <= 16 && wide_for(G, fix) && ctx->stream2) {  // (gangs of 32: the 65 536 workgroups of config 2 that leave at once cost K1 1 - 2 %: measured)
-      int rr = ensure(ctx, ctx->d_wide_res, n_it * sizeof(SegResult));
-      if (rr) return rr;
-      if ((rr = ensure(ctx, ctx->d_cold2, n_it * (size_t)KG_COLD_STRIDE))) return rr;  // (only the large items' slots are touched)
-      TBZ_HIP(hipEventRecord(ctx->evw[0], ctx->stream));  // (the items are there)
-      TBZ_HIP(hipStreamWaitEvent(ctx->stream2, ctx->evw[0], 0));
-      K1gParams kw{(const u8*)d_in, pool_tok(fix), pool_runs(fix), pool_half(fix), 1, d_items, (SegResult*)ctx->d_wide_res.p,
-                   d_markers_cur, d_first_marker, nullptr, nullptr, (u32)n_mark, (u32)n_it, ovl_for(64), sub_min_for(64),
-                   wide_for(G, fix), resume_abs, (u8*)ctx->d_cold2.p};
+  }
+  return 0;
+}
+static int launch_k1(Call& c, const Item* d_items, SegResult* d_res, size_t n_it, bool fix) {
+  tbz_ctx* ctx = c.ctx;
+  int G = k1_gang(c, n_it);
+  if (G == 1 && pool_half(c, fix)) G = 8;  // (a repair launch of many small items into a pool laid out for gangs)
+  if (!fix) ctx->tim.k1_gang = (uint32_t)G;
+  if (G == 1) return launch_lane(c, d_items, d_res, n_it, fix);
+  size_t per = 64 / G, nwg = (n_it + per - 1) / per;
+  // A launch of NARROW gangs (short items) declines the few items that are far larger than its mean (SEG_WIDE).
+  // Gangs of 64 take exactly those — a second kernel over the same item list on the second stream, every workgroup of
+  // which leaves at once unless its item is such a one — BESIDE the narrow launch instead of after the host has read
+  // its results (config 5: one 294 Kbit block among 3 548 items: 0.77 + 0.8 ms one after the other).  Their results
+  // go to an array of their own (the narrow gang writes SEG_WIDE into the item's record).
+  if (!fix && G <= 16 && wide_for(ctx, G, fix) && ctx->stream2) {  // (gangs of 32: the 65 536 workgroups of config 2 that leave at once cost K1 1 - 2 %: measured)
+    int rr = ensure(ctx, ctx->d_wide_res, n_it * sizeof(SegResult));
+    if (rr) return rr;
+    if ((rr = ensure(ctx, ctx->d_cold2, n_it * (size_t)KG_COLD_STRIDE))) return rr;  // (only the large items' slots are touched)
+    TBZ_HIP(hipEventRecord(ctx->evw[0], ctx->stream));  // (the items are there)
+    TBZ_HIP(hipStreamWaitEvent(ctx->stream2, ctx->evw[0], 0));
+    K1gParams kw = k1g_params(c, d_items, (SegResult*)ctx->d_wide_res.p, n_it, 64, fix, false, (u8*)ctx->d_cold2.p);
+    kw.only_wide = 1;
+    kw.wide_bits = wide_for(ctx, G, fix);
+    TBZ_LAUNCH(tbz_k1g64_huff_decode, n_it, ctx->stream2, kw);
+    TBZ_HIP(hipEventRecord(ctx->evw[1], ctx->stream2));
+    c.wide_beside = true;
+  }
+  // K1h: every lane parses the first block header of its own item, so that the gangs need not (their leaders
+  // would do it with 2 of 64 lanes busy)
+  int rr;
+  if ((rr = ensure(ctx, ctx->d_scratch, n_it * (size_t)K1_SCRATCH))) return rr;
+  if ((rr = ensure(ctx, ctx->d_hdr, n_it * sizeof(HdrRec)))) return rr;
+  if (G >= 32 && (rr = ensure(ctx, ctx->d_cold, n_it * (size_t)KG_COLD_STRIDE))) return rr;  // (narrower gangs keep their lists in LDS)
+  K1hParams kh{(const u8*)c.d_in, d_items, (u8*)ctx->d_scratch.p, (HdrRec*)ctx->d_hdr.p, (u32)n_it};
+  if (ctx->k1h) TBZ_LAUNCH(tbz_k1h_headers, (n_it + 63) / 64, ctx->stream, kh);
+  K1gParams kg = k1g_params(c, d_items, d_res, n_it, G, fix, false, (u8*)ctx->d_cold.p);
+  kg.hdr = ctx->k1h ? (const HdrRec*)ctx->d_hdr.p : nullptr;
+  kg.hdr_lens = (const u8*)ctx->d_scratch.p;
+  kg.wide_bits = wide_for(ctx, G, fix);
 #ifdef TBZ_WAVE_TRACE
-      kw.trace = nullptr;
-#endif
-      TBZ_LAUNCH(tbz_k1g64_huff_decode, n_it, ctx->stream2, kw);
-      TBZ_HIP(hipEventRecord(ctx->evw[1], ctx->stream2));
-      wide_beside = true;
-    }
-    // K1h: every lane parses the first block header of its own item, so that the gangs need not (their leaders
-    // would do it with 2 of 64 lanes busy)
-    int rr;
-    if ((rr = ensure(ctx, ctx->d_scratch, n_it * (size_t)K1_SCRATCH))) return rr;
-    if ((rr = ensure(ctx, ctx->d_hdr, n_it * sizeof(HdrRec)))) return rr;
-    if (G >= 32 && (rr = ensure(ctx, ctx->d_cold, n_it * (size_t)KG_COLD_STRIDE))) return rr;  // (narrower gangs keep their lists in LDS)
-    K1hParams kh{(const u8*)d_in, d_items, (u8*)ctx->d_scratch.p, (HdrRec*)ctx->d_hdr.p, (u32)n_it};
-    if (ctx->k1h) TBZ_LAUNCH(tbz_k1h_headers, (n_it + 63) / 64, ctx->stream, kh);
-    K1gParams kg{(const u8*)d_in, pool_tok(fix), pool_runs(fix), pool_half(fix), 0, d_items, d_res,
-                 d_markers_cur, d_first_marker, ctx->k1h ? (const HdrRec*)ctx->d_hdr.p : nullptr,
-                 (const u8*)ctx->d_scratch.p, (u32)n_mark, (u32)n_it, ovl_for(G), sub_min_for(G), wide_for(G, fix), resume_abs,
-                 (u8*)ctx->d_cold.p};
-#ifdef TBZ_WAVE_TRACE
-    {
-      static int n_launch = 0;
-      u32 ef = (n_launch++ >= 1 && getenv("TBZ_EXP")) ? (u32)atoi(getenv("TBZ_EXP")) : 0u;
-      hipMemcpyToSymbolAsync(HIP_SYMBOL(tbz_exp_flags), &ef, 4, 0, hipMemcpyHostToDevice, ctx->stream);
+  {
+    static int n_launch = 0;
+    u32 ef = (n_launch++ >= 1 && getenv("TBZ_EXP")) ? (u32)atoi(getenv("TBZ_EXP")) : 0u;
+    hipMemcpyToSymbolAsync(HIP_SYMBOL(tbz_exp_flags), &ef, 4, 0, hipMemcpyHostToDevice, ctx->stream);
+    hipStreamSynchronize(ctx->stream);
+  }
+  static u64* d_trace = nullptr;
+  static size_t trace_wg = 0;
+  if (const char* tp = getenv("TBZ_WAVE_TRACE")) {
+    if (d_trace && trace_wg) {  // the previous launch's records
+      std::vector<u64> h(trace_wg * 16);
       hipStreamSynchronize(ctx->stream);
+      hipMemcpy(h.data(), d_trace, h.size() * 8, hipMemcpyDeviceToHost);
+      if (FILE* f = fopen(tp, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+      hipFree(d_trace);
     }
-    static u64* d_trace = nullptr;
-    static size_t trace_wg = 0;
-    if (const char* tp = getenv("TBZ_WAVE_TRACE")) {
-      if (d_trace && trace_wg) {  // the previous launch's records
-        std::vector<u64> h(trace_wg * 16);
-        hipStreamSynchronize(ctx->stream);
-        hipMemcpy(h.data(), d_trace, h.size() * 8, hipMemcpyDeviceToHost);
-        if (FILE* f = fopen(tp, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-        hipFree(d_trace);
-      }
-      hipMalloc((void**)&d_trace, nwg * 128);
-      hipMemsetAsync(d_trace, 0, nwg * 128, ctx->stream);
-      trace_wg = nwg;
-      kg.trace = d_trace;
-
-    } else {
-      kg.trace = nullptr;
-    }
+    hipMalloc((void**)&d_trace, nwg * 128);
+    hipMemsetAsync(d_trace, 0, nwg * 128, ctx->stream);
+    trace_wg = nwg;
+    kg.trace = d_trace;
+  }
 #endif
-    switch (G) {
-      case 8: TBZ_LAUNCH(tbz_k1g8_huff_decode, nwg, ctx->stream, kg); break;
-      case 16: TBZ_LAUNCH(tbz_k1g16_huff_decode, nwg, ctx->stream, kg); break;
-      case 32: TBZ_LAUNCH(tbz_k1g32_huff_decode, nwg, ctx->stream, kg); break;
-      default: TBZ_LAUNCH(tbz_k1g64_huff_decode, nwg, ctx->stream, kg); break;
-    }
-    if (wide_beside && !fix) TBZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->evw[1], 0));  // what follows needs both
-    return 0;
-  };
-  // K3 (layout on the device when every item simply lands on its successor): its stream tables go up before
-  // K1 so that nothing but two tiny kernels and a 16-byte read-back stand between K1 and the decision
+  switch (G) {
+    case 8: TBZ_LAUNCH(tbz_k1g8_huff_decode, nwg, ctx->stream, kg); break;
+    case 16: TBZ_LAUNCH(tbz_k1g16_huff_decode, nwg, ctx->stream, kg); break;
+    case 32: TBZ_LAUNCH(tbz_k1g32_huff_decode, nwg, ctx->stream, kg); break;
+    default: TBZ_LAUNCH(tbz_k1g64_huff_decode, nwg, ctx->stream, kg); break;
+  }
+  if (c.wide_beside && !fix) TBZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->evw[1], 0));  // what follows needs both
+  return 0;
+}
+
+// ---------------------------------------------------------------- K1 main launch (events 2 / 3) + K3 verdict
+// K3 (layout on the device when every item simply lands on its successor): its stream tables go up before
+// K1 so that nothing but two tiny kernels and a 16-byte read-back stand between K1 and the decision
+static int call_k1(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n, n_items = c.n_items;
   const bool try_simple = !ctx->host_layout && n_items != 0;
   const u32 k3_tiles = (u32)((n_items + K3_TILE - 1) / K3_TILE);
-  K3Params k3{};
+  int r;
   if (try_simple) {
     std::vector<uint32_t> fi(n), ni(n);
     std::vector<uint64_t> oo(n), oc(n);
     for (size_t s = 0; s < n; s++) {
-      fi[s] = sp[s].first_item;
-      ni[s] = sp[s].n_items;
-      oo[s] = sp[s].out_off;
-      oc[s] = size_only ? 0 : sp[s].out_cap;
+      fi[s] = c.sp[s].first_item;
+      ni[s] = c.sp[s].n_items;
+      oo[s] = c.sp[s].out_off;
+      oc[s] = c.size_only ? 0 : c.sp[s].out_cap;
     }
     if ((r = upload(ctx, ctx->d_k3_fi, fi))) return r;
     if ((r = upload(ctx, ctx->d_k3_ni, ni))) return r;
@@ -1458,278 +1489,261 @@ static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, co
     if ((r = ensure(ctx, ctx->d_groups, n_items * sizeof(Group)))) return r;
     if ((r = ensure(ctx, ctx->d_k3_streams, (n + 1) * sizeof(K3Stream)))) return r;
     if ((r = ensure(ctx, ctx->d_k3_glob, sizeof(K3Global)))) return r;
-    k3 = K3Params{(const Item*)ctx->d_items.p, (const SegResult*)ctx->d_res.p, (const u32*)ctx->d_k3_fi.p,
-                  (const u32*)ctx->d_k3_ni.p, (const u64*)ctx->d_k3_oo.p, (const u64*)ctx->d_k3_oc.p,
-                  (u64*)ctx->d_k3_sums.p, (u64*)ctx->d_k3_flags.p, (u64*)ctx->d_k3_gscan.p, (u32*)ctx->d_k3_gne.p,
-                  (Seg*)ctx->d_segs.p, (Group*)ctx->d_groups.p, (K3Stream*)ctx->d_k3_streams.p,
-                  (K3Global*)ctx->d_k3_glob.p, (u32)n_items, k3_tiles, (u32)n};
+    c.k3 = K3Params{(const Item*)ctx->d_items.p, (const SegResult*)ctx->d_res.p, (const u32*)ctx->d_k3_fi.p,
+                    (const u32*)ctx->d_k3_ni.p, (const u64*)ctx->d_k3_oo.p, (const u64*)ctx->d_k3_oc.p,
+                    (u64*)ctx->d_k3_sums.p, (u64*)ctx->d_k3_flags.p, (u64*)ctx->d_k3_gscan.p, (u32*)ctx->d_k3_gne.p,
+                    (Seg*)ctx->d_segs.p, (Group*)ctx->d_groups.p, (K3Stream*)ctx->d_k3_streams.p,
+                    (K3Global*)ctx->d_k3_glob.p, (u32)n_items, k3_tiles, (u32)n};
   }
   if ((r = record(ctx, 2))) return r;
-  if ((r = launch_k1((const Item*)ctx->d_items.p, (SegResult*)ctx->d_res.p, n_items, false))) return r;
+  if ((r = launch_k1(c, (const Item*)ctx->d_items.p, (SegResult*)ctx->d_res.p, n_items, false))) return r;
   TBZ_HIP(hipGetLastError());
   if ((r = record(ctx, 3))) return r;
   ctx->tim.huff_launches = 1;
-  bool simple = false;
-  bool fused_adler = false;  // adler32 partials come from K2 (simple path, zlib, all groups in the two-wave kernel)
   char* pin_k3 = (char*)ctx->h_pin + (((n + 5) * 4 + 15) & ~(size_t)15);
-  K3Global* h_glob = (K3Global*)pin_k3;
-  K3Stream* h_k3s = (K3Stream*)(pin_k3 + sizeof(K3Global));
-  if (try_simple) {
-    TBZ_LAUNCH(tbz_k3_tile_sums, k3_tiles, ctx->stream, k3);
-    TBZ_LAUNCH(tbz_k3_scan_tiles, 1, ctx->stream, k3);
-    TBZ_HIP(hipMemcpyAsync(h_glob, ctx->d_k3_glob.p, sizeof(K3Global), hipMemcpyDeviceToHost, ctx->stream));
-    TBZ_HIP(hipStreamSynchronize(ctx->stream));
-    simple = h_glob->not_simple == 0;
-    // an item far larger than a fair share of the output is sliced (tbz_k3_slice): the general path lays that out
-    if (simple && ctx->sym_hist && !size_only) {
-      uint64_t target = std::max<uint64_t>(64u << 10, h_glob->total_out / 4096);
-      if (ctx->tun.slice) target = std::max(1024, ctx->tun.slice);
-      if (h_glob->max_out >= 2 * target) simple = false;
-    }
+  c.h_glob = (K3Global*)pin_k3;
+  c.h_k3s = (K3Stream*)(pin_k3 + sizeof(K3Global));
+  if (!try_simple) return 0;
+  TBZ_LAUNCH(tbz_k3_tile_sums, k3_tiles, ctx->stream, c.k3);
+  TBZ_LAUNCH(tbz_k3_scan_tiles, 1, ctx->stream, c.k3);
+  if ((r = read_back(ctx, c.h_glob, ctx->d_k3_glob.p, sizeof(K3Global)))) return r;
+  c.simple = c.h_glob->not_simple == 0;
+  // an item far larger than a fair share of the output is sliced (tbz_k3_slice): the general path lays that out
+  if (c.simple && ctx->sym_hist && !c.size_only) {
+    uint64_t target = std::max<uint64_t>(64u << 10, c.h_glob->total_out / 4096);
+    if (ctx->tun.slice) target = std::max(1024, ctx->tun.slice);
+    if (c.h_glob->max_out >= 2 * target) c.simple = false;
   }
-  // what a stream reports once its status is known (both layout paths)
-  auto fill_result = [&](size_t s, int32_t status, uint32_t nseg, bool error_first = false) {
-    StreamPlan& S = sp[s];
-    tbz_result& R = results[s];
-    // 3bz decodes front to back: it reports overflow as soon as a token does not fit, before it
-    // could meet a later error / underrun
-    uint64_t cap = S.out_cap;
-    // … and inside a stored block it asks for output space before it asks for input (copy-byte-or-fail,
-    // deflate.lisp:538-573): payload cut off exactly where the buffer is full is output-overflow
-    bool overflow = (S.total_out > cap || (S.stored_cut && status == TBZ_INPUT_UNDERRUN && S.total_out == cap)) && !error_first;
-    if (overflow) status = TBZ_OUTPUT_OVERFLOW;
-    R.status = status;
-    R.segments = nseg;
-    R.out_total = S.total_out;
-    R.out_len = overflow ? cap : S.total_out;
-    // not finished: the last flush boundary (octet offset just after its 00 00 FF FF) the block chain landed on
-    // — everything before it is decoded and delivered, a decoder may be restarted there (tbz_amd.h)
-    R.in_consumed = S.saw_final ? (S.in_end_bit / 8 - S.in_off)
-                                : (S.boundary_bit / 8 > S.in_off ? S.boundary_bit / 8 - S.in_off : 0);
-    R.boundary_out = S.saw_final ? S.total_out : (S.boundary_bit / 8 > S.in_off ? S.boundary_out : 0);
-    R.trailer_check = S.trailer0;
-    R.trailer_isize = S.trailer1;
-    if (S.saw_final) R.flags |= 2;
-    if (S.stored_cut) R.flags |= 4;
-    if (status < 0) R.out_len = 0;  // reference signals an error: no partial-result contract
-    return status;
-  };
-  float huff_ms = 0;
-  if (simple) {
-    // ---------------------------------------------------------------- device layout + K2, host reads n+1 records
-    TBZ_LAUNCH(tbz_k3_scan_items, k3_tiles, ctx->stream, k3);
-    TBZ_LAUNCH(tbz_k3_emit, k3_tiles, ctx->stream, k3);
-    TBZ_HIP(hipMemcpyAsync(h_k3s, ctx->d_k3_streams.p, (n + 1) * sizeof(K3Stream), hipMemcpyDeviceToHost, ctx->stream));
-    TBZ_HIP(hipEventRecord(ctx->ev[7], ctx->stream));
-    if ((r = record(ctx, 4))) return r;
-    if (!size_only && opt && opt->alloc) {  // the buffer comes once the size is known: wait for the stream record
-      TBZ_HIP(hipEventSynchronize(ctx->ev[7]));
-      d_out = opt->alloc(h_k3s[0].total_out);
-      if (!d_out) return TBZ_E_NOMEM;
-    }
-    if (!size_only) {
-      if (!d_out) return TBZ_E_ARG;
-      const u32 n_it = (u32)n_items;
-      fused_adler = format == TBZ_FORMAT_ZLIB && !ctx->k2_single && h_glob->n_big == 0 && !ctx->tun.no_fused_adler;
-      K2Params k2{(const Seg*)ctx->d_segs.p, (const Group*)ctx->d_groups.p, nullptr,
-                  (const u8*)d_in, (u8*)d_out, n_it, 0, 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr, 0};
-      if (h_glob->n_big < n_it) {
-        k2.win_bytes = (u32)((h_glob->max_small + K2_SLACK + 63) & ~63ull);
-        k2.cls = h_glob->n_big ? 1 : 0;
-        if (fused_adler) {  // every group goes through the two-wave kernel: it leaves the adler32 partials behind
-          if ((r = ensure(ctx, ctx->d_gck, (size_t)n_it * sizeof(CkPartial)))) return r;
-          if ((r = ensure(ctx, ctx->d_gchunks, (size_t)n_it * sizeof(CkChunk)))) return r;
-          k2.gck = (CkPartial*)ctx->d_gck.p;
-          k2.gchunks = (CkChunk*)ctx->d_gchunks.p;
-        }
-        ctx->tim.k2_kinds |= ctx->k2_single ? 2u : 1u;
-        if (ctx->k2_single)
-          TBZ_LAUNCH_DYN(tbz_k2_lz77_small, n_it, k2.win_bytes + 2 * K2_TOKBUF + 512, ctx->stream, k2);
-        else
-          TBZ_LAUNCH_DYN_WG(tbz_k2_lz77_dual, n_it, 128, k2.win_bytes + 2 * K2_TOKBUF + 512 + 2 * sizeof(K2Hand),
-                            ctx->stream, k2);
-      }
-#ifdef TBZ_WAVE_TRACE
-      if (const char* vp = getenv("TBZ_K2_TRACE")) {
-        std::vector<u64> h(8192 * 8);
-        hipStreamSynchronize(ctx->stream);
-        u32 cn[4] = {0, 0, 0, 0};
-        hipMemcpyFromSymbol(cn, HIP_SYMBOL(tbz_dbg_cnt), 16);
-        fprintf(stderr, "tbz: K2 resolve since the start: %u batches with matches, %.2f rounds and %.1f matches per batch\n", cn[0],
-                cn[0] ? (double)cn[1] / cn[0] : 0.0, cn[0] ? (double)cn[2] / cn[0] : 0.0);
-        hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(tbz_dbg), h.size() * 8);
-        if (FILE* f = fopen(vp, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-      }
-#endif
-      if (h_glob->n_big) {
-        k2.win_bytes = 0;
-        k2.cls = h_glob->n_big < n_it ? 2 : 0;
-        ctx->tim.k2_kinds |= 4u;
-        if (ctx->k2_single) TBZ_LAUNCH(tbz_k2_lz77, n_it, ctx->stream, k2);
-        else if (ctx->k2_ring2) TBZ_LAUNCH_WG(tbz_k2_lz77_ring2, n_it, 128, ctx->stream, k2);
-        else TBZ_LAUNCH_WG(tbz_k2_lz77_ring3, n_it, 192, ctx->stream, k2);
-      }
-      TBZ_HIP(hipGetLastError());
-    }
-    if ((r = record(ctx, 5))) return r;
-    TBZ_HIP(hipEventSynchronize(ctx->ev[7]));  // the stream records are here; K2 keeps running
-    huff_ms = elapsed(ctx, 2, 3);
-    ctx->tim.huff_ms = huff_ms;
-    ctx->tim.token_words = h_k3s[n].tok_words;
-    ctx->tim.n_segments = ctx->tim.n_groups = h_k3s[n].nonempty;
-    for (size_t s = 0; s < n; s++) {
-      StreamPlan& S = sp[s];
-      const K3Stream& k = h_k3s[s];
-      S.total_out = k.total_out;
-      S.saw_final = k.last.status == SEG_FINAL;  // else: the last item ran out of input (every other one landed)
-      S.trailer0 = k.last.trailer0;
-      S.trailer1 = k.last.trailer1;
-      S.trailer_have = k.last.trailer_have;
-      S.in_end_bit = k.last.end_bit;
-      S.boundary_bit = (S.n_items > 1 && !(k.last_start & 7)) ? k.last_start : 0;
-      S.boundary_out = k.total_out - k.last.out_bytes;
-      if (k.last.status == SEG_UNDERRUN) {
-        S.blk_known = true;
-        if (k.last.land_marker == 0) {
-          S.blk_bit = (uint64_t)k.last.trailer0 | ((uint64_t)k.last.trailer1 << 32);
-          S.blk_out = k.total_out - k.last.out_bytes + k.last.reserved;
-        } else {
-          S.blk_bit = k.last_start;
-          S.blk_out = k.total_out - k.last.out_bytes;
-        }
-        S.hdr_bit = (uint64_t)k.last.trailer0 | ((uint64_t)k.last.trailer1 << 32);
-      }
-      S.stored_cut = k.last.status == SEG_UNDERRUN && k.last.pad == 2;
-      if (k.last.status == SEG_UNDERRUN && k.last.pad == 1 && !(k.last.end_bit & 7)) {
-        S.boundary_bit = k.last.end_bit;
-        S.boundary_out = k.total_out;
-      }
-      S.status = S.saw_final ? TBZ_FINISHED : TBZ_INPUT_UNDERRUN;
-      S.done = true;
-      fill_result(s, S.status, (uint32_t)k.nonempty);
-    }
-  } else {
-  if ((r = fetch_host_tables())) return r;
-  std::vector<SegResult> res(n_items);
-  TBZ_HIP(hipMemcpyAsync(res.data(), ctx->d_res.p, res.size() * sizeof(SegResult), hipMemcpyDeviceToHost,
-                         ctx->stream));
-  TBZ_HIP(hipStreamSynchronize(ctx->stream));
-  huff_ms = elapsed(ctx, 2, 3);
-  if (wide_beside) {
-    bool any = false;
-    for (const SegResult& q : res) any = any || q.status == SEG_WIDE;
-    if (any) {
-      std::vector<SegResult> wr(n_items);
-      TBZ_HIP(hipMemcpyAsync(wr.data(), ctx->d_wide_res.p, wr.size() * sizeof(SegResult), hipMemcpyDeviceToHost, ctx->stream));
-      TBZ_HIP(hipStreamSynchronize(ctx->stream));
-      for (size_t i = 0; i < n_items; i++)
-        if (res[i].status == SEG_WIDE) res[i] = wr[i];
-      ctx->tim.huff_launches++;
-    }
+  return 0;
+}
+// what a stream reports once its status is known (both layout paths)
+static int32_t fill_result(Call& c, size_t s, int32_t status, uint32_t nseg, bool error_first = false) {
+  StreamPlan& S = c.sp[s];
+  tbz_result& R = c.results[s];
+  // 3bz decodes front to back: it reports overflow as soon as a token does not fit, before it
+  // could meet a later error / underrun
+  uint64_t cap = S.out_cap;
+  // … and inside a stored block it asks for output space before it asks for input (copy-byte-or-fail,
+  // deflate.lisp:538-573): payload cut off exactly where the buffer is full is output-overflow
+  bool overflow = (S.total_out > cap || (S.stored_cut && status == TBZ_INPUT_UNDERRUN && S.total_out == cap)) && !error_first;
+  if (overflow) status = TBZ_OUTPUT_OVERFLOW;
+  R.status = status;
+  R.segments = nseg;
+  R.out_total = S.total_out;
+  R.out_len = overflow ? cap : S.total_out;
+  // not finished: the last flush boundary (octet offset just after its 00 00 FF FF) the block chain landed on
+  // — everything before it is decoded and delivered, a decoder may be restarted there (tbz_amd.h)
+  R.in_consumed = S.saw_final ? (S.in_end_bit / 8 - S.in_off)
+                              : (S.boundary_bit / 8 > S.in_off ? S.boundary_bit / 8 - S.in_off : 0);
+  R.boundary_out = S.saw_final ? S.total_out : (S.boundary_bit / 8 > S.in_off ? S.boundary_out : 0);
+  R.trailer_check = S.trailer0;
+  R.trailer_isize = S.trailer1;
+  if (S.saw_final) R.flags |= 2;
+  if (S.stored_cut) R.flags |= 4;
+  if (status < 0) R.out_len = 0;  // reference signals an error: no partial-result contract
+  return status;
+}
+// a stream whose input ran out in the item that began at bit item_start (its result q; S.total_out counts q's
+// octets): where a resumed decode would start (CoreOpts), a stored block cut off, a boundary at an aligned block start
+static void note_underrun(StreamPlan& S, const SegResult& q, uint64_t item_start) {
+  S.stored_cut = q.pad == 2;
+  S.blk_known = true;
+  if (q.land_marker == 0) {  // the block in which the input ran out (K1 reports its start and the octets before it)
+    S.blk_bit = (uint64_t)q.trailer0 | ((uint64_t)q.trailer1 << 32);
+    S.blk_out = S.total_out - q.out_bytes + q.reserved;
+  } else {                   // only the item's start is known exactly
+    S.blk_bit = item_start;
+    S.blk_out = S.total_out - q.out_bytes;
   }
-  if ((r = redo(items, res, false))) return r;
+  S.hdr_bit = (uint64_t)q.trailer0 | ((uint64_t)q.trailer1 << 32);
+  if (q.pad == 1 && !(q.end_bit & 7)) {  // ran out exactly at an octet-aligned block start
+    S.boundary_bit = q.end_bit;
+    S.boundary_out = S.total_out;
+  }
+}
+// the output buffer, when the caller hands it out once the size is known (CoreOpts::alloc); `ready`: an event to wait
+// for first (`total` is read after it: a read-back)
+static int alloc_out(Call& c, const uint64_t& total, hipEvent_t ready = nullptr) {
+  tbz_ctx* ctx = c.ctx;
+  if (c.size_only || !c.opt || !c.opt->alloc) return 0;
+  if (ready) TBZ_HIP(hipEventSynchronize(ready));
+  c.d_out = c.opt->alloc(total);
+  return c.d_out ? 0 : TBZ_E_NOMEM;
+}
 
-  // ---------------------------------------------------------------- chain walk (+ fix-up rounds)
-  std::vector<SegHost> segs;
-  segs.reserve(n_items);
-  std::vector<std::vector<SegHost>> per_stream(n);
-  auto consume = [&](StreamPlan& S, size_t s, const Item& it, const SegResult& q, bool is_fixup) {
-    SegHost h;
-    h.item = it;
-    h.seg.tok = q.tok;
-    h.seg.tok_words = q.tok_words;
-    h.seg.out_bytes = q.out_bytes;
-    h.seg.n_runs = q.n_runs;
-    h.seg.run_first = 0;
-    h.seg.runs = q.runs;
-    h.seg.run0 = q.run0;
-    h.stream = (uint32_t)s;
-    h.deficit = q.max_deficit;
-    h.continues = S.next_continues;
-    S.next_continues = false;
-    if (ctx->tun.debug2) fprintf(stderr, "consume: start_bit %llu status %d end_bit %llu out %llu tok %llu runs %u deficit %u fixup %d\n", (unsigned long long)it.start_bit, q.status, (unsigned long long)q.end_bit, (unsigned long long)q.out_bytes, (unsigned long long)q.tok_words, q.n_runs, q.max_deficit, (int)is_fixup);
-    if (q.tok_words || q.out_bytes) per_stream[s].push_back(h);
-    else if (h.continues) S.next_continues = true;  // nothing emitted: carry the flag forward
-    S.total_out += q.out_bytes;
-    ctx->tim.token_words += q.tok_words;
-    if (q.status != SEG_UNDERRUN) {
-      ctx->gang_rounds += q.reserved >> 32;
-      ctx->gang_valid += q.reserved & 0xffffffffu;
-    }
-    if (q.status == SEG_LANDED) {
-      uint32_t mk = is_fixup ? q.land_marker : 0;
-      if (is_fixup) S.cur_item = S.first_item + 1 + (mk - S.first_marker);
-      else S.cur_item += 1;
-      if (S.cur_item < S.first_item + S.n_items && !(items[S.cur_item].start_bit & 7)) {
-        S.boundary_bit = items[S.cur_item].start_bit;  // (octet-aligned boundaries only: that is what in_consumed can say)
-        S.boundary_out = S.total_out;
+// ---------------------------------------------------------------- device layout + K2, host reads n+1 records
+static int call_device_layout(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
+  const K3Global* g = c.h_glob;
+  int r;
+  TBZ_LAUNCH(tbz_k3_scan_items, c.k3.n_tiles, ctx->stream, c.k3);
+  TBZ_LAUNCH(tbz_k3_emit, c.k3.n_tiles, ctx->stream, c.k3);
+  TBZ_HIP(hipMemcpyAsync(c.h_k3s, ctx->d_k3_streams.p, (n + 1) * sizeof(K3Stream), hipMemcpyDeviceToHost, ctx->stream));
+  TBZ_HIP(hipEventRecord(ctx->ev[7], ctx->stream));
+  if ((r = record(ctx, 4))) return r;
+  if ((r = alloc_out(c, c.h_k3s[0].total_out, ctx->ev[7]))) return r;  // (the stream record first)
+  if (!c.size_only) {
+    if (!c.d_out) return TBZ_E_ARG;
+    const u32 n_it = (u32)c.n_items;
+    c.fused_adler = c.format == TBZ_FORMAT_ZLIB && !ctx->k2_single && g->n_big == 0 && !ctx->tun.no_fused_adler;
+    K2Params k2{(const Seg*)ctx->d_segs.p, (const Group*)ctx->d_groups.p, nullptr,
+                (const u8*)c.d_in, (u8*)c.d_out, n_it, 0, 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr, 0};
+    if (g->n_big < n_it) {
+      k2.cls = g->n_big ? 1 : 0;
+      if (c.fused_adler) {  // every group goes through the two-wave kernel: it leaves the adler32 partials behind
+        if ((r = ensure(ctx, ctx->d_gck, (size_t)n_it * sizeof(CkPartial)))) return r;
+        if ((r = ensure(ctx, ctx->d_gchunks, (size_t)n_it * sizeof(CkChunk)))) return r;
+        k2.gck = (CkPartial*)ctx->d_gck.p;
+        k2.gchunks = (CkChunk*)ctx->d_gchunks.p;
       }
-      return;
+      launch_k2_linear(ctx, k2, n_it, g->max_small);
     }
-    if (q.status == SEG_FINAL) {
-      S.saw_final = true;
-      S.trailer0 = q.trailer0;
-      S.trailer1 = q.trailer1;
-      S.trailer_have = q.trailer_have;
-      S.in_end_bit = q.end_bit;
-      S.status = TBZ_FINISHED;
-      S.done = true;
-      return;
+    k2_trace(ctx);
+    if (g->n_big) {
+      k2.win_bytes = 0;
+      k2.cls = g->n_big < n_it ? 2 : 0;
+      launch_k2_ring(ctx, k2, n_it);
     }
-    if (q.status == SEG_OVERSHOOT) {
-      S.pending_fixup = true;
-      S.fix_start_bit = q.end_bit;
-      S.next_continues = true;
-      return;
-    }
-    if (q.status == SEG_UNDERRUN) {
-      S.status = TBZ_INPUT_UNDERRUN;
-      S.in_end_bit = q.end_bit;
-      S.stored_cut = q.pad == 2;
-      S.blk_known = true;
-      if (q.land_marker == 0) {  // the block in which the input ran out (K1 reports its start and the octets before it)
-        S.blk_bit = (uint64_t)q.trailer0 | ((uint64_t)q.trailer1 << 32);
-        S.blk_out = S.total_out - q.out_bytes + q.reserved;
-      } else {                   // only the item's start is known exactly
-        S.blk_bit = it.start_bit;
-        S.blk_out = S.total_out - q.out_bytes;
-      }
-      S.hdr_bit = (uint64_t)q.trailer0 | ((uint64_t)q.trailer1 << 32);
-      if (q.pad == 1 && !(q.end_bit & 7)) {  // ran out exactly at an octet-aligned block start
-        S.boundary_bit = q.end_bit;
-        S.boundary_out = S.total_out;
-      }
-      S.done = true;
-      return;
-    }
-    S.status = q.status < 0 ? q.status : TBZ_E_INTERNAL;
-    S.done = true;
-  };
-  for (size_t s = 0; s < n; s++) {
-    StreamPlan& S = sp[s];
-    while (!S.done && !S.pending_fixup) {
-      if (S.cur_item >= S.first_item + S.n_items) {  // cannot happen: the last item has no limit
-        S.status = TBZ_E_INTERNAL;
-        S.done = true;
-        break;
-      }
-      consume(S, s, items[S.cur_item], res[S.cur_item], false);
-    }
+    TBZ_HIP(hipGetLastError());
   }
+  if ((r = record(ctx, 5))) return r;
+  TBZ_HIP(hipEventSynchronize(ctx->ev[7]));  // the stream records are here; K2 keeps running
+  c.huff_ms = elapsed(ctx, 2, 3);
+  ctx->tim.huff_ms = c.huff_ms;
+  ctx->tim.token_words = c.h_k3s[n].tok_words;
+  ctx->tim.n_segments = ctx->tim.n_groups = c.h_k3s[n].nonempty;
+  for (size_t s = 0; s < n; s++) {
+    StreamPlan& S = c.sp[s];
+    const K3Stream& k = c.h_k3s[s];
+    S.total_out = k.total_out;
+    S.saw_final = k.last.status == SEG_FINAL;  // else: the last item ran out of input (every other one landed)
+    S.trailer0 = k.last.trailer0;
+    S.trailer1 = k.last.trailer1;
+    S.trailer_have = k.last.trailer_have;
+    S.in_end_bit = k.last.end_bit;
+    S.boundary_bit = (S.n_items > 1 && !(k.last_start & 7)) ? k.last_start : 0;
+    S.boundary_out = k.total_out - k.last.out_bytes;
+    if (k.last.status == SEG_UNDERRUN) note_underrun(S, k.last, k.last_start);
+    S.status = S.saw_final ? TBZ_FINISHED : TBZ_INPUT_UNDERRUN;
+    S.done = true;
+    fill_result(c, s, S.status, (uint32_t)k.nonempty);
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------- host path: the main launch's results (+ wide, redo)
+static int call_host_results(Call& c, std::vector<SegResult>& res) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n_items = c.n_items;
+  int r;
+  if (c.items.empty()) {  // the general layout path walks the items on the host
+    c.items.resize(n_items);
+    if ((r = read_back(ctx, c.items.data(), ctx->d_items.p, n_items * sizeof(Item)))) return r;
+  }
+  res.resize(n_items);
+  if ((r = read_back(ctx, res.data(), ctx->d_res.p, res.size() * sizeof(SegResult)))) return r;
+  c.huff_ms = elapsed(ctx, 2, 3);
+  if (c.wide_beside && std::any_of(res.begin(), res.end(), [](const SegResult& q) { return q.status == SEG_WIDE; })) {
+    std::vector<SegResult> wr(n_items);
+    if ((r = read_back(ctx, wr.data(), ctx->d_wide_res.p, wr.size() * sizeof(SegResult)))) return r;
+    for (size_t i = 0; i < n_items; i++)
+      if (res[i].status == SEG_WIDE) res[i] = wr[i];
+    ctx->tim.huff_launches++;
+  }
+  return redo(c, c.items, res, false);
+}
+
+// ---------------------------------------------------------------- chain walk (+ fix-up rounds)
+static void consume(Call& c, size_t s, const Item& it, const SegResult& q, bool is_fixup) {
+  tbz_ctx* ctx = c.ctx;
+  StreamPlan& S = c.sp[s];
+  SegHost h;
+  h.item = it;
+  h.seg.tok = q.tok;
+  h.seg.tok_words = q.tok_words;
+  h.seg.out_bytes = q.out_bytes;
+  h.seg.n_runs = q.n_runs;
+  h.seg.run_first = 0;
+  h.seg.runs = q.runs;
+  h.seg.run0 = q.run0;
+  h.deficit = q.max_deficit;
+  h.continues = S.next_continues;
+  S.next_continues = false;
+  if (ctx->tun.debug2) fprintf(stderr, "consume: start_bit %llu status %d end_bit %llu out %llu tok %llu runs %u deficit %u fixup %d\n", (unsigned long long)it.start_bit, q.status, (unsigned long long)q.end_bit, (unsigned long long)q.out_bytes, (unsigned long long)q.tok_words, q.n_runs, q.max_deficit, (int)is_fixup);
+  if (q.tok_words || q.out_bytes) c.per_stream[s].push_back(h);
+  else if (h.continues) S.next_continues = true;  // nothing emitted: carry the flag forward
+  S.total_out += q.out_bytes;
+  ctx->tim.token_words += q.tok_words;
+  if (q.status != SEG_UNDERRUN) {
+    ctx->gang_rounds += q.reserved >> 32;
+    ctx->gang_valid += q.reserved & 0xffffffffu;
+  }
+  if (q.status == SEG_LANDED) {
+    if (is_fixup) S.cur_item = S.first_item + 1 + (q.land_marker - S.first_marker);
+    else S.cur_item += 1;
+    if (S.cur_item < S.first_item + S.n_items && !(c.items[S.cur_item].start_bit & 7)) {
+      S.boundary_bit = c.items[S.cur_item].start_bit;  // (octet-aligned boundaries only: that is what in_consumed can say)
+      S.boundary_out = S.total_out;
+    }
+    return;
+  }
+  if (q.status == SEG_FINAL) {
+    S.saw_final = true;
+    S.trailer0 = q.trailer0;
+    S.trailer1 = q.trailer1;
+    S.trailer_have = q.trailer_have;
+    S.in_end_bit = q.end_bit;
+    S.status = TBZ_FINISHED;
+    S.done = true;
+    return;
+  }
+  if (q.status == SEG_OVERSHOOT) {
+    S.pending_fixup = true;
+    S.fix_start_bit = q.end_bit;
+    S.next_continues = true;
+    return;
+  }
+  if (q.status == SEG_UNDERRUN) {
+    S.status = TBZ_INPUT_UNDERRUN;
+    S.in_end_bit = q.end_bit;
+    note_underrun(S, q, it.start_bit);
+    S.done = true;
+    return;
+  }
+  S.status = q.status < 0 ? q.status : TBZ_E_INTERNAL;
+  S.done = true;
+}
+// stream s's chain of the main launch's items, from its current one until it ends or needs a repair
+static void walk(Call& c, size_t s, const std::vector<SegResult>& res) {
+  StreamPlan& S = c.sp[s];
+  while (!S.done && !S.pending_fixup) {
+    if (S.cur_item >= S.first_item + S.n_items) {  // cannot happen: the last item has no limit
+      S.status = TBZ_E_INTERNAL;
+      S.done = true;
+      break;
+    }
+    consume(c, s, c.items[S.cur_item], res[S.cur_item], false);
+  }
+}
+static int call_chain_walk(Call& c, const std::vector<SegResult>& res) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
+  int r;
+  c.per_stream.resize(n);
+  for (size_t s = 0; s < n; s++) walk(c, s, res);
   for (;;) {
     std::vector<Item> fix;
-    std::vector<size_t> fix_stream;
     for (size_t s = 0; s < n; s++)
-      if (sp[s].pending_fixup && !sp[s].done) {
+      if (c.sp[s].pending_fixup && !c.sp[s].done) {
         Item it{};
-        it.start_bit = sp[s].fix_start_bit;
+        it.start_bit = c.sp[s].fix_start_bit;
         it.limit_bit = ~0ull;
-        it.end_byte = sp[s].in_off + sp[s].in_len;
+        it.end_byte = c.sp[s].in_off + c.sp[s].in_len;
         it.stream = (uint32_t)s;
-        it.flags = ((uint32_t)format << ITEM_FMT_SHIFT) | ITEM_FIXUP;
-        if (resume_abs && s == 0 && it.start_bit == sp[0].in_off * 8 + bit_off) it.flags |= ITEM_RESUME;  // (the block the session resumes in)
+        it.flags = ((uint32_t)c.format << ITEM_FMT_SHIFT) | ITEM_FIXUP;
+        if (c.resume_abs && s == 0 && it.start_bit == c.sp[0].in_off * 8 + c.bit_off) it.flags |= ITEM_RESUME;  // (the block the session resumes in)
         fix.push_back(it);
-        fix_stream.push_back(s);
       }
     if (fix.empty()) break;
     ctx->tim.fixup_rounds++;
@@ -1745,153 +1759,131 @@ static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, co
         hi = std::max(hi, fix[k].end_byte * 8);
       }
       if (ctx->tim.fixup_rounds == 1) {
-        pool2_base = lo & ~(uint64_t)((1u << RUN_SHIFT) - 1);
-        pool2_hi = 0;
+        c.pool2_base = lo & ~(uint64_t)((1u << RUN_SHIFT) - 1);
+        c.pool2_hi = 0;
       }
-      if (lo < pool2_base) return TBZ_E_INTERNAL;  // (cannot happen: a stream's repairs move forward)
-      if (hi > pool2_hi) {
+      if (lo < c.pool2_base) return TBZ_E_INTERNAL;  // (cannot happen: a stream's repairs move forward)
+      if (hi > c.pool2_hi) {
         // growing would move tokens that segments already refer to: size for the whole tail of the call at once
-        if (pool2_hi != 0) return TBZ_E_INTERNAL;
-        pool2_hi = in_extent * 8;
-        const uint64_t bits2 = pool2_hi - pool2_base;
-        half2 = (k1_gang(fix.size()) == 1 || ctx->tun.tok_full) ? 0u : 1u;
-        if ((r = ensure(ctx, ctx->d_tok2, ((size_t)bits2 >> half2) * 2 + 256))) return r;
-        if ((r = ensure(ctx, ctx->d_runs2, ((size_t)bits2 >> RUN_SHIFT) * sizeof(RunRec) + 1024))) return r;
+        if (c.pool2_hi != 0) return TBZ_E_INTERNAL;
+        c.pool2_hi = c.in_extent * 8;
+        if ((r = size_pool(c, fix.size(), c.pool2_hi - c.pool2_base, ctx->d_tok2, ctx->d_runs2, c.half2))) return r;
       }
     }
-    if ((r = launch_k1((const Item*)ctx->d_items.p, (SegResult*)ctx->d_res.p, fix.size(), true))) return r;
+    if ((r = launch_k1(c, (const Item*)ctx->d_items.p, (SegResult*)ctx->d_res.p, fix.size(), true))) return r;
     TBZ_HIP(hipGetLastError());
     if ((r = record(ctx, 3))) return r;
     ctx->tim.huff_launches++;
     std::vector<SegResult> fr(fix.size());
-    TBZ_HIP(hipMemcpyAsync(fr.data(), ctx->d_res.p, fr.size() * sizeof(SegResult), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    TBZ_HIP(hipStreamSynchronize(ctx->stream));
-    huff_ms += elapsed(ctx, 2, 3);
-    if ((r = redo(fix, fr, true))) return r;
+    if ((r = read_back(ctx, fr.data(), ctx->d_res.p, fr.size() * sizeof(SegResult)))) return r;
+    c.huff_ms += elapsed(ctx, 2, 3);
+    if ((r = redo(c, fix, fr, true))) return r;
     for (size_t k = 0; k < fix.size(); k++) {
-      size_t s = fix_stream[k];
-      StreamPlan& S = sp[s];
-      S.pending_fixup = false;
-      consume(S, s, fix[k], fr[k], true);
-      while (!S.done && !S.pending_fixup) {
-        if (S.cur_item >= S.first_item + S.n_items) {
-          S.status = TBZ_E_INTERNAL;
-          S.done = true;
-          break;
-        }
-        consume(S, s, items[S.cur_item], res[S.cur_item], false);
-      }
+      const size_t s = fix[k].stream;
+      c.sp[s].pending_fixup = false;
+      consume(c, s, fix[k], fr[k], true);
+      walk(c, s, res);
     }
   }
-  ctx->tim.huff_ms = huff_ms;
+  ctx->tim.huff_ms = c.huff_ms;
   if (ctx->tun.debug) fprintf(stderr, "tbz: gang rounds %llu, committed lanes %llu (%.2f per round)\n", (unsigned long long)ctx->gang_rounds, (unsigned long long)ctx->gang_valid, ctx->gang_rounds ? (double)ctx->gang_valid / ctx->gang_rounds : 0.0);
+  return 0;
+}
 
-  // ---------------------------------------------------------------- distance errors vs output overflow
-  // history check (deflate.lisp:343-345): a match may not reach before the stream's first octet.  Every segment
-  // here lies before the point where the stream ended / failed, so a front-to-back decoder meets this error
-  // before any later one — and before output-overflow iff the offending match STARTS at or before the buffer's
-  // end.  K1 reports per item only the largest reach-back; when the buffer ends inside the offending segment
-  // that item is decoded once more by the one-lane kernel, told how many octets precede it (ITEM_HIST), which
-  // then reports the first offending match's output offset.
-  enum { DIST_NONE = 0, DIST_FIRST = 1, DIST_AFTER_OVERFLOW = 2 };
-  std::vector<uint8_t> dist_first(n, DIST_NONE);
-  uint64_t dist_at = ~0ull;  // (sessions: one stream)
-  {
-    struct Probe { size_t s, seg; uint64_t before; };
-    std::vector<Probe> probes[1];
-    for (size_t s = 0; s < n; s++) {
-      uint64_t produced = 0;
-      const uint64_t hist = s == 0 ? hist_len : 0;  // (a resumed stream: octets of earlier output that are there to copy from)
-      for (size_t i = 0; i < per_stream[s].size(); i++) {
-        const SegHost& h = per_stream[s][i];
-        if (h.deficit && (uint64_t)h.deficit > produced + hist) {
-          const uint64_t end = produced + h.seg.out_bytes, cap = sp[s].out_cap;
-          if (opt && opt->prefix_on_error) probes[0].push_back({s, i, produced + hist});  // (a session wants the place)
-          else if (cap >= end) dist_first[s] = DIST_FIRST;
-          else if (cap < produced) dist_first[s] = DIST_AFTER_OVERFLOW;
-          else probes[0].push_back({s, i, produced + hist});
-          break;
-        }
-        produced += h.seg.out_bytes;
+// ---------------------------------------------------------------- distance errors vs output overflow
+// history check (deflate.lisp:343-345): a match may not reach before the stream's first octet.  Every segment
+// here lies before the point where the stream ended / failed, so a front-to-back decoder meets this error
+// before any later one — and before output-overflow iff the offending match STARTS at or before the buffer's
+// end.  K1 reports per item only the largest reach-back; when the buffer ends inside the offending segment
+// that item is decoded once more by the one-lane kernel, told how many octets precede it (ITEM_HIST), which
+// then reports the first offending match's output offset.
+static int call_distance(Call& c) {
+  const size_t n = c.n;
+  c.dist_first.assign(n, DIST_NONE);
+  struct Probe { size_t s, seg; uint64_t before; };
+  std::vector<Probe> pv;
+  for (size_t s = 0; s < n; s++) {
+    uint64_t produced = 0;
+    const uint64_t hist = s == 0 ? c.hist_len : 0;  // (a resumed stream: octets of earlier output that are there to copy from)
+    for (size_t i = 0; i < c.per_stream[s].size(); i++) {
+      const SegHost& h = c.per_stream[s][i];
+      if (h.deficit && (uint64_t)h.deficit > produced + hist) {
+        const uint64_t end = produced + h.seg.out_bytes, cap = c.sp[s].out_cap;
+        if (c.opt && c.opt->prefix_on_error) pv.push_back({s, i, produced + hist});  // (a session wants the place)
+        else if (cap >= end) c.dist_first[s] = DIST_FIRST;
+        else if (cap < produced) c.dist_first[s] = DIST_AFTER_OVERFLOW;
+        else pv.push_back({s, i, produced + hist});
+        break;
       }
-    }
-    if (!probes[0].empty()) {
-      auto& pv = probes[0];
-      std::vector<Item> its(pv.size());
-      for (size_t k = 0; k < pv.size(); k++) {
-        its[k] = per_stream[pv[k].s][pv[k].seg].item;
-        its[k].flags |= ITEM_PROBE | ((uint32_t)std::min<uint64_t>(pv[k].before, 65535) << ITEM_HIST_SHIFT);  // < 32768: the item's reach-back exceeds it
-      }
-      if ((r = make_explicit(its))) return r;
-      if ((r = upload(ctx, ctx->d_redo_items, its))) return r;
-      if ((r = ensure(ctx, ctx->d_redo_res, its.size() * sizeof(SegResult)))) return r;
-      if ((r = launch_lane((const Item*)ctx->d_redo_items.p, (SegResult*)ctx->d_redo_res.p, its.size(), false, true))) return r;
-      std::vector<SegResult> pr(its.size());
-      TBZ_HIP(hipMemcpyAsync(pr.data(), ctx->d_redo_res.p, pr.size() * sizeof(SegResult), hipMemcpyDeviceToHost,
-                             ctx->stream));
-      TBZ_HIP(hipStreamSynchronize(ctx->stream));
-      ctx->tim.huff_launches++;
-      for (size_t k = 0; k < pv.size(); k++) {
-        SegHost& h = per_stream[pv[k].s][pv[k].seg];
-        // the item's tokens are now the one-lane kernel's (same octets, one run)
-        h.seg.tok = pr[k].tok;
-        h.seg.tok_words = pr[k].tok_words;
-        h.seg.n_runs = pr[k].n_runs;
-        h.seg.run0 = pr[k].run0;
-        const uint64_t at = pr[k].reserved;  // octets into the item; ~0: none found (cannot happen)
-        const uint64_t hist_k = pv[k].s == 0 ? hist_len : 0;
-        dist_first[pv[k].s] = (at != ~0ull && pv[k].before - hist_k + at > sp[pv[k].s].out_cap) ? DIST_AFTER_OVERFLOW : DIST_FIRST;
-        if (at != ~0ull) dist_at = pv[k].before - hist_k + at;  // octets of the stream before the offending match
-      }
+      produced += h.seg.out_bytes;
     }
   }
+  if (pv.empty()) return 0;
+  std::vector<Item> its(pv.size());
+  for (size_t k = 0; k < pv.size(); k++) {
+    its[k] = c.per_stream[pv[k].s][pv[k].seg].item;
+    its[k].flags |= ITEM_PROBE | ((uint32_t)std::min<uint64_t>(pv[k].before, 65535) << ITEM_HIST_SHIFT);  // < 32768: the item's reach-back exceeds it
+  }
+  std::vector<SegResult> pr;
+  int r;
+  if ((r = k1_again(c, its, REDO_LANE, false, pr))) return r;
+  for (size_t k = 0; k < pv.size(); k++) {
+    SegHost& h = c.per_stream[pv[k].s][pv[k].seg];
+    // the item's tokens are now the one-lane kernel's (same octets, one run)
+    h.seg.tok = pr[k].tok;
+    h.seg.tok_words = pr[k].tok_words;
+    h.seg.n_runs = pr[k].n_runs;
+    h.seg.run0 = pr[k].run0;
+    const uint64_t at = pr[k].reserved;  // octets into the item; ~0: none found (cannot happen)
+    const uint64_t hist_k = pv[k].s == 0 ? c.hist_len : 0;
+    c.dist_first[pv[k].s] = (at != ~0ull && pv[k].before - hist_k + at > c.sp[pv[k].s].out_cap) ? DIST_AFTER_OVERFLOW : DIST_FIRST;
+    if (at != ~0ull) c.dist_at = pv[k].before - hist_k + at;  // octets of the stream before the offending match
+  }
+  return 0;
+}
 
-  // ---------------------------------------------------------------- per-stream layout, groups, status
-  std::vector<Seg> h_segs;
-  std::vector<Group> h_groups;
-  std::vector<uint8_t> h_hist;      // per group: 1 = H-group (symbolic history)
-  std::vector<uint32_t> h_gstream;  // per group: its stream
-  std::vector<int32_t> h_grec;      // per group: index of the slice record that describes it (tbz_k3_slice), or -1
-  std::vector<BigSeg> bigs;
-  uint32_t n_recs = 0;
+// ---------------------------------------------------------------- per-stream layout, groups, status
+static int call_groups(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
+  CoreOpts* opt = c.opt;
   // K2's parallelism is its number of groups: segments much larger than a fair share of the call's output are cut
   // into slices at run boundaries on the device (tbz_k3_slice); every slice becomes a group
   uint64_t slice_target = 64u << 10, h_join_below = 48u << 10;
   {
     uint64_t tot = 0;
-    for (size_t s = 0; s < n; s++) tot += std::min(sp[s].total_out, sp[s].out_cap);
+    for (size_t s = 0; s < n; s++) tot += std::min(c.sp[s].total_out, c.sp[s].out_cap);
     slice_target = std::max<uint64_t>(slice_target, tot / 4096);
     if (ctx->tun.slice) slice_target = std::max(1024, ctx->tun.slice);  // (tests force small slices)
     h_join_below = std::min<uint64_t>(std::max<uint64_t>(48u << 10, tot / 2048), 256u << 10);
     if (ctx->tun.h_join) h_join_below = std::max(1024, ctx->tun.h_join);
   }
   for (size_t s = 0; s < n; s++) {
-    StreamPlan& S = sp[s];
-    tbz_result& R = results[s];
-    auto& v = per_stream[s];
+    StreamPlan& S = c.sp[s];
+    tbz_result& R = c.results[s];
+    auto& v = c.per_stream[s];
     int32_t status = S.status;
-    if (dist_first[s] != DIST_NONE) status = TBZ_E_DISTANCE;
-    status = fill_result(s, status, (uint32_t)v.size(), dist_first[s] == DIST_FIRST);
+    if (c.dist_first[s] != DIST_NONE) status = TBZ_E_DISTANCE;
+    status = fill_result(c, s, status, (uint32_t)v.size(), c.dist_first[s] == DIST_FIRST);
     if (status < 0) {
       // reference signals an error: no partial-result contract.  A session hands out what a front-to-back decoder
       // produced before it met the error: everything before the failing token (for a match that reaches before the
       // stream's first octet the one-lane re-decode above found its place)
-      if (!(opt && opt->prefix_on_error) || (status == TBZ_E_DISTANCE && dist_at == ~0ull)) continue;
+      if (!(opt && opt->prefix_on_error) || (status == TBZ_E_DISTANCE && c.dist_at == ~0ull)) continue;
       opt->first_error = status;
-      R.out_len = status == TBZ_E_DISTANCE ? dist_at : S.total_out;
+      R.out_len = status == TBZ_E_DISTANCE ? c.dist_at : S.total_out;
       R.out_total = R.out_len;
     }
-    if (size_only) continue;
-    const uint64_t hist = s == 0 ? hist_len : 0;
+    if (c.size_only) continue;
+    const uint64_t hist = s == 0 ? c.hist_len : 0;
     // groups: consecutive segments that share one LZ77 window in one K2 workgroup.  A segment that needs no history
     // opens a group of its own.  One that does (its matches reach before its first octet, or it continues a
     // repaired block) joins the group before it while that group is small; a group whose segments reach before
     // ITS first octet becomes an H-group: decoded against symbolic history, resolved by K6 (so the groups of a
     // stream without flush points run in parallel instead of collapsing into one workgroup).
     uint64_t o = 0;
-    S.seg_first = (uint32_t)h_segs.size();
-    const size_t g0 = h_groups.size();  // this stream's first group
+    S.seg_first = (uint32_t)c.h_segs.size();
+    const size_t g0 = c.h_groups.size();  // this stream's first group
     // a group keeps taking in history-needing segments below this size: K6's chain grows with the cube root of their number, so
     // groups grow with the call's output while the ring kernel still gets some 2048 of them (x 2 planes)
     const uint64_t H_JOIN_BELOW = h_join_below;
@@ -1908,114 +1900,114 @@ static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, co
         b.out_abs = S.out_off + o;
         b.out_end = S.out_off + R.out_len;
         b.target = slice_target;
-        b.seg_slot = (uint32_t)h_segs.size();
-        b.group_slot = (uint32_t)h_groups.size();
-        b.rec_slot = n_recs;
+        b.seg_slot = (uint32_t)c.h_segs.size();
+        b.group_slot = (uint32_t)c.h_groups.size();
+        b.rec_slot = c.n_recs;
         b.n_slots = (uint32_t)(v[i].seg.out_bytes / slice_target + 1);
-        b.first_hist = (need && reach < b.out_abs && (h_groups.size() > g0 || hist > 0)) ? 1u : 0u;
-        bigs.push_back(b);
+        b.first_hist = (need && reach < b.out_abs && (c.h_groups.size() > g0 || hist > 0)) ? 1u : 0u;
+        c.bigs.push_back(b);
         for (uint32_t k = 0; k < b.n_slots; k++) {
           Group g{};
           g.out_abs = b.out_abs;
           g.out_end = b.out_end;
           g.seg_first = b.seg_slot + k;
-          h_groups.push_back(g);
-          h_hist.push_back(0);
-          h_grec.push_back((int32_t)(n_recs + k));
-          h_segs.push_back(Seg{});
+          c.h_groups.push_back(g);
+          c.h_hist.push_back(0);
+          c.h_grec.push_back((int32_t)(c.n_recs + k));
+          c.h_segs.push_back(Seg{});
         }
-        n_recs += b.n_slots;
+        c.n_recs += b.n_slots;
         o += v[i].seg.out_bytes;
         after_big = true;
         continue;
       }
-      bool join = need && !after_big && h_groups.size() > g0;
-      if (ctx->sym_hist && join) join = (S.out_off + o) - h_groups.back().out_abs < H_JOIN_BELOW;
+      bool join = need && !after_big && c.h_groups.size() > g0;
+      if (ctx->sym_hist && join) join = (S.out_off + o) - c.h_groups.back().out_abs < H_JOIN_BELOW;
       after_big = false;
       if (!join) {
         Group g;
         g.out_abs = S.out_off + o;
         g.out_end = S.out_off + R.out_len;
-        g.seg_first = (uint32_t)h_segs.size();
+        g.seg_first = (uint32_t)c.h_segs.size();
         g.seg_count = 0;
-        h_groups.push_back(g);
-        h_hist.push_back(0);
-        h_grec.push_back(-1);
+        c.h_groups.push_back(g);
+        c.h_hist.push_back(0);
+        c.h_grec.push_back(-1);
       }
-      if (need && reach < h_groups.back().out_abs) {
-        if (ctx->sym_hist && (h_groups.size() > g0 + 1 || hist > 0)) {
-          h_hist.back() = 1;
+      if (need && reach < c.h_groups.back().out_abs) {
+        if (ctx->sym_hist && (c.h_groups.size() > g0 + 1 || hist > 0)) {
+          c.h_hist.back() = 1;
         } else {
           // (round-1 scheme, and always for a stream's first group) take in earlier groups until the history is covered
-          while (h_groups.size() > g0 + 1 && h_groups.back().out_abs > reach) {
-            const uint32_t cnt = h_groups.back().seg_count;
-            const uint8_t hh = h_hist.back();
-            h_groups.pop_back();
-            h_hist.pop_back();
-            h_grec.pop_back();
-            h_groups.back().seg_count += cnt;
-            h_hist.back() |= hh;
+          while (c.h_groups.size() > g0 + 1 && c.h_groups.back().out_abs > reach) {
+            const uint32_t cnt = c.h_groups.back().seg_count;
+            const uint8_t hh = c.h_hist.back();
+            c.h_groups.pop_back();
+            c.h_hist.pop_back();
+            c.h_grec.pop_back();
+            c.h_groups.back().seg_count += cnt;
+            c.h_hist.back() |= hh;
           }
         }
       }
-      h_groups.back().seg_count++;
-      h_segs.push_back(v[i].seg);
+      c.h_groups.back().seg_count++;
+      c.h_segs.push_back(v[i].seg);
       o += v[i].seg.out_bytes;
     }
-    S.seg_count = (uint32_t)h_segs.size() - S.seg_first;
-    for (size_t gi = g0; gi < h_groups.size(); gi++) h_gstream.push_back((uint32_t)s);
+    S.seg_count = (uint32_t)c.h_segs.size() - S.seg_first;
+    for (size_t gi = g0; gi < c.h_groups.size(); gi++) c.h_gstream.push_back((uint32_t)s);
   }
-  ctx->tim.n_segments = h_segs.size();
-  ctx->tim.n_groups = h_groups.size();
+  ctx->tim.n_segments = c.h_segs.size();
+  ctx->tim.n_groups = c.h_groups.size();
+  return 0;
+}
 
-  // ---------------------------------------------------------------- K2
+// ---------------------------------------------------------------- host path: K2 (+ slices, H-groups and K6)
+static int call_host_k2(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  int r;
   if ((r = record(ctx, 4))) return r;
-  if (!size_only && opt && opt->alloc) {
-    d_out = opt->alloc(sp[0].total_out);
-    if (!d_out) return TBZ_E_NOMEM;
-  }
-  if (!size_only && !h_groups.empty()) {
-    if (!d_out) return TBZ_E_ARG;
-    if ((r = upload(ctx, ctx->d_segs, h_segs))) return r;
-    if ((r = upload(ctx, ctx->d_groups, h_groups))) return r;
-    std::vector<SliceRec> recs(n_recs);
-    if (!bigs.empty()) {
-      if ((r = upload(ctx, ctx->d_bigs, bigs))) return r;
-      if ((r = ensure(ctx, ctx->d_recs, (size_t)n_recs * sizeof(SliceRec)))) return r;
+  if ((r = alloc_out(c, c.sp[0].total_out))) return r;
+  if (!c.size_only && !c.h_groups.empty()) {
+    if (!c.d_out) return TBZ_E_ARG;
+    if ((r = upload(ctx, ctx->d_segs, c.h_segs))) return r;
+    if ((r = upload(ctx, ctx->d_groups, c.h_groups))) return r;
+    std::vector<SliceRec> recs(c.n_recs);
+    if (!c.bigs.empty()) {
+      if ((r = upload(ctx, ctx->d_bigs, c.bigs))) return r;
+      if ((r = ensure(ctx, ctx->d_recs, (size_t)c.n_recs * sizeof(SliceRec)))) return r;
       K3sParams ks{(const BigSeg*)ctx->d_bigs.p,
-                   (Seg*)ctx->d_segs.p, (Group*)ctx->d_groups.p, (SliceRec*)ctx->d_recs.p, (u32)bigs.size()};
-      TBZ_LAUNCH(tbz_k3_slice, bigs.size(), ctx->stream, ks);
-      TBZ_HIP(hipMemcpyAsync(recs.data(), ctx->d_recs.p, (size_t)n_recs * sizeof(SliceRec), hipMemcpyDeviceToHost, ctx->stream));
-      TBZ_HIP(hipStreamSynchronize(ctx->stream));
-      for (size_t gi = 0; gi < h_groups.size(); gi++)
-        if (h_grec[gi] >= 0) {
-          const SliceRec& q = recs[h_grec[gi]];
-          h_groups[gi].out_abs = q.out_abs;
-          h_groups[gi].seg_count = q.used ? 1u : 0u;
-          h_hist[gi] = (uint8_t)(q.used && q.hist);
+                   (Seg*)ctx->d_segs.p, (Group*)ctx->d_groups.p, (SliceRec*)ctx->d_recs.p, (u32)c.bigs.size()};
+      TBZ_LAUNCH(tbz_k3_slice, c.bigs.size(), ctx->stream, ks);
+      if ((r = read_back(ctx, recs.data(), ctx->d_recs.p, (size_t)c.n_recs * sizeof(SliceRec)))) return r;
+      for (size_t gi = 0; gi < c.h_groups.size(); gi++)
+        if (c.h_grec[gi] >= 0) {
+          const SliceRec& q = recs[c.h_grec[gi]];
+          c.h_groups[gi].out_abs = q.out_abs;
+          c.h_groups[gi].seg_count = q.used ? 1u : 0u;
+          c.h_hist[gi] = (uint8_t)(q.used && q.hist);
         }
     }
-    // groups whose whole output fits a linear LDS window (the common case: flush-delimited segments)
-    // run with dynamic LDS sized to the largest of them; the rest take the 32 KiB-history ring kernel;
+    // groups whose whole output fits a linear LDS window run with the linear kernels; the rest take the ring kernel;
     // H-groups take the ring kernel twice (octet plane, pointer plane) and K6 afterwards
     std::vector<uint32_t> order_small, order_big, order_h;
     std::vector<HGroupSpan> hgs;
     uint64_t max_small = 0, mark_lo = ~0ull, mark_hi = 0;
-    for (size_t gi = 0; gi < h_groups.size(); gi++) {
+    for (size_t gi = 0; gi < c.h_groups.size(); gi++) {
       uint64_t tot = 0;
-      if (h_grec[gi] >= 0) {
-        if (!recs[h_grec[gi]].used) continue;  // an empty slot: no workgroup at all
-        tot = recs[h_grec[gi]].out_bytes;
+      if (c.h_grec[gi] >= 0) {
+        if (!recs[c.h_grec[gi]].used) continue;  // an empty slot: no workgroup at all
+        tot = recs[c.h_grec[gi]].out_bytes;
       } else {
-        for (uint32_t k = 0; k < h_groups[gi].seg_count; k++) tot += h_segs[h_groups[gi].seg_first + k].out_bytes;
+        for (uint32_t k = 0; k < c.h_groups[gi].seg_count; k++) tot += c.h_segs[c.h_groups[gi].seg_first + k].out_bytes;
       }
-      if (h_hist[gi]) {
-        const StreamPlan& S = sp[h_gstream[gi]];
+      if (c.h_hist[gi]) {
+        const StreamPlan& S = c.sp[c.h_gstream[gi]];
         order_h.push_back((uint32_t)gi);
-        hgs.push_back(HGroupSpan{h_groups[gi].out_abs, std::max(h_groups[gi].out_abs, std::min(h_groups[gi].out_abs + tot, h_groups[gi].out_end)),
-                         S.out_off - (h_gstream[gi] == 0 ? hist_len : 0), h_gstream[gi]});
+        hgs.push_back(HGroupSpan{c.h_groups[gi].out_abs, std::max(c.h_groups[gi].out_abs, std::min(c.h_groups[gi].out_abs + tot, c.h_groups[gi].out_end)),
+                         S.out_off - (c.h_gstream[gi] == 0 ? c.hist_len : 0), c.h_gstream[gi]});
         mark_lo = std::min(mark_lo, S.out_off);
-        mark_hi = std::max(mark_hi, h_groups[gi].out_end);
+        mark_hi = std::max(mark_hi, c.h_groups[gi].out_end);
       } else if (tot + K2_SLACK <= K2_SMALL_MAX) {
         order_small.push_back((uint32_t)gi);
         max_small = std::max(max_small, tot);
@@ -2028,108 +2020,89 @@ static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, co
     order.insert(order.end(), order_h.begin(), order_h.end());
     ctx->tim.n_groups = order.size();
     if ((r = upload(ctx, ctx->d_order, order))) return r;
-    K2Params k2{(const Seg*)ctx->d_segs.p, (const Group*)ctx->d_groups.p, (const u32*)ctx->d_order.p, (const u8*)d_in, (u8*)d_out, 0, 0, 0, nullptr, nullptr,
+    K2Params k2{(const Seg*)ctx->d_segs.p, (const Group*)ctx->d_groups.p, (const u32*)ctx->d_order.p, (const u8*)c.d_in, (u8*)c.d_out, 0, 0, 0, nullptr, nullptr,
                 0, 0, 0, 0, 0, nullptr, 0};
     if (!order_small.empty()) {
       k2.n_groups = (u32)order_small.size();
-      k2.win_bytes = (u32)((max_small + K2_SLACK + 63) & ~63ull);
-      ctx->tim.k2_kinds |= ctx->k2_single ? 2u : 1u;
-      if (ctx->k2_single)
-        TBZ_LAUNCH_DYN(tbz_k2_lz77_small, order_small.size(), k2.win_bytes + 2 * K2_TOKBUF + 512, ctx->stream, k2);
-      else
-        TBZ_LAUNCH_DYN_WG(tbz_k2_lz77_dual, order_small.size(), 128,
-                          k2.win_bytes + 2 * K2_TOKBUF + 512 + 2 * sizeof(K2Hand), ctx->stream, k2);
-#ifdef TBZ_WAVE_TRACE
-      if (const char* vp = getenv("TBZ_K2_TRACE")) {
-        std::vector<u64> h(8192 * 8);
-        hipStreamSynchronize(ctx->stream);
-        u32 cn[4] = {0, 0, 0, 0};
-        hipMemcpyFromSymbol(cn, HIP_SYMBOL(tbz_dbg_cnt), 16);
-        fprintf(stderr, "tbz: K2 resolve since the start: %u batches with matches, %.2f rounds and %.1f matches per batch\n", cn[0],
-                cn[0] ? (double)cn[1] / cn[0] : 0.0, cn[0] ? (double)cn[2] / cn[0] : 0.0);
-        hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(tbz_dbg), h.size() * 8);
-        if (FILE* f = fopen(vp, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-      }
-#endif
+      launch_k2_linear(ctx, k2, order_small.size(), max_small);
+      k2_trace(ctx);
     }
     if (!order_big.empty() && order_h.empty()) {
       k2.order = (const u32*)ctx->d_order.p + order_small.size();
       k2.n_groups = (u32)order_big.size();
       k2.win_bytes = 0;
-      ctx->tim.k2_kinds |= 4u;
-      if (ctx->k2_single) TBZ_LAUNCH(tbz_k2_lz77, order_big.size(), ctx->stream, k2);
-      else if (ctx->k2_ring2) TBZ_LAUNCH_WG(tbz_k2_lz77_ring2, order_big.size(), 128, ctx->stream, k2);
-        else TBZ_LAUNCH_WG(tbz_k2_lz77_ring3, order_big.size(), 192, ctx->stream, k2);
+      launch_k2_ring(ctx, k2, order_big.size());
     }
-    if (!order_h.empty()) {
-      if ((r = hgroups_launch(ctx, hgs, k2, order_small.size(), order_big.size(), order_h.size(), d_out, mark_lo, mark_hi))) return r;
-      have_resolve = true;
-    }
+    if (!order_h.empty() && (r = hgroups_launch(ctx, hgs, k2, order_small.size(), order_big.size(), order_h.size(), c.d_out, mark_lo, mark_hi)))
+      return r;
     TBZ_HIP(hipGetLastError());
   }
-  if ((r = record(ctx, 5))) return r;
-  }  // !simple
+  return record(ctx, 5);
+}
 
-  // ---------------------------------------------------------------- K4 / K5 + trailer compare
-  if (!size_only && format != TBZ_FORMAT_DEFLATE) {
+// ---------------------------------------------------------------- K4 / K5 + trailer compare, CoreOpts outputs, timings
+static int call_finish(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
+  const int format = c.format;
+  const bool size_only = c.size_only;
+  CoreOpts* opt = c.opt;
+  const StreamPlan& S0 = c.sp[0];
+  int r;
+  if (size_only || format == TBZ_FORMAT_DEFLATE) {
+    TBZ_HIP(hipStreamSynchronize(ctx->stream));
+  } else {
     std::vector<uint64_t> co(n), cl(n);
     std::vector<uint32_t> init(n), sums;
     for (size_t s = 0; s < n; s++) {
-      co[s] = sp[s].out_off;
+      co[s] = c.sp[s].out_off;
       // update-checksum runs when finished or output-overflow (zlib.lisp:136-137, gzip.lisp:268-269)
-      bool want = results[s].status == TBZ_FINISHED || results[s].status == TBZ_OUTPUT_OVERFLOW;
-      cl[s] = want ? results[s].out_len : 0;
+      bool want = c.results[s].status == TBZ_FINISHED || c.results[s].status == TBZ_OUTPUT_OVERFLOW;
+      cl[s] = want ? c.results[s].out_len : 0;
       init[s] = format == TBZ_FORMAT_ZLIB ? 1u : 0u;  // s1=1,s2=0 (zlib.lisp:11-12) / crc 0 (gzip.lisp:28)
     }
-    if (fused_adler) {
+    if (c.fused_adler) {
       std::vector<uint32_t> fg(n), ng(n);
       for (size_t s = 0; s < n; s++) {
-        fg[s] = sp[s].first_item;
-        ng[s] = sp[s].n_items;
+        fg[s] = c.sp[s].first_item;
+        ng[s] = c.sp[s].n_items;
       }
       if ((r = run_adler_groups(ctx, fg, ng, init, sums))) return r;
-    } else if ((r = run_checksums(ctx, format == TBZ_FORMAT_ZLIB ? 1 : 2, d_out, co, cl, init, sums))) {
+    } else if ((r = run_checksums(ctx, format == TBZ_FORMAT_ZLIB ? 1 : 2, c.d_out, co, cl, init, sums))) {
       return r;
     }
     for (size_t s = 0; s < n; s++) {
-      tbz_result& R = results[s];
+      tbz_result& R = c.results[s];
       if (cl[s] == 0) sums[s] = init[s];  // (the fused partials cover whatever K2 wrote)
       if (format == TBZ_FORMAT_ZLIB) R.adler32 = sums[s];
       else R.crc32 = sums[s];
     }
-  } else {
-    TBZ_HIP(hipStreamSynchronize(ctx->stream));
   }
   if ((r = record(ctx, 6))) return r;
   TBZ_HIP(hipStreamSynchronize(ctx->stream));
   const bool keep_prefix = opt && opt->prefix_on_error;
   if (opt) {
-    opt->blk_known = sp[0].blk_known;
-    opt->blk_bit = sp[0].blk_bit > sp[0].in_off * 8 ? sp[0].blk_bit - sp[0].in_off * 8 : 0;
-    opt->blk_out = sp[0].blk_out;
-    opt->hdr_bit = sp[0].hdr_bit > sp[0].in_off * 8 ? sp[0].hdr_bit - sp[0].in_off * 8 : 0;
-    opt->tok_bit = sp[0].in_end_bit > sp[0].in_off * 8 ? sp[0].in_end_bit - sp[0].in_off * 8 : 0;
-    opt->end_bit = sp[0].in_end_bit > sp[0].in_off * 8 ? sp[0].in_end_bit - sp[0].in_off * 8 : 0;
+    opt->blk_known = S0.blk_known;
+    opt->blk_bit = S0.blk_bit > S0.in_off * 8 ? S0.blk_bit - S0.in_off * 8 : 0;
+    opt->blk_out = S0.blk_out;
+    opt->hdr_bit = S0.hdr_bit > S0.in_off * 8 ? S0.hdr_bit - S0.in_off * 8 : 0;
+    opt->tok_bit = opt->end_bit = S0.in_end_bit > S0.in_off * 8 ? S0.in_end_bit - S0.in_off * 8 : 0;
   }
-  for (size_t s = 0; s < n; s++) {
-    tbz_result& R = results[s];
-    StreamPlan& S = sp[s];
+  for (size_t s = 0; s < c.n; s++) {
+    tbz_result& R = c.results[s];
+    const StreamPlan& S = c.sp[s];
     if (R.status != TBZ_FINISHED || format == TBZ_FORMAT_DEFLATE) continue;
-    if (format == TBZ_FORMAT_ZLIB) {
-      if (S.trailer_have < 2) R.status = TBZ_INPUT_UNDERRUN;  // zlib.lisp:81-86
-      else if (size_only) R.flags |= 0;
-      else if (S.trailer0 != R.adler32) { R.status = TBZ_E_ADLER32; R.out_len = keep_prefix ? R.out_len : 0; }
-      else R.flags |= 1;
-    } else {
-      if (S.trailer_have < 1) R.status = TBZ_INPUT_UNDERRUN;  // gzip.lisp:83-86
-      else if (!size_only && S.trailer0 != R.crc32) { R.status = TBZ_E_CRC32; R.out_len = keep_prefix ? R.out_len : 0; }
-      else if (S.trailer_have < 2) R.status = TBZ_INPUT_UNDERRUN;  // gzip.lisp:96-99
-      else if (!size_only) R.flags |= 1;
-    }
+    const bool zlib = format == TBZ_FORMAT_ZLIB;
+    if (S.trailer_have < (zlib ? 2u : 1u)) R.status = TBZ_INPUT_UNDERRUN;  // zlib.lisp:81-86, gzip.lisp:83-86
+    else if (!size_only && S.trailer0 != (zlib ? R.adler32 : R.crc32)) {
+      R.status = zlib ? TBZ_E_ADLER32 : TBZ_E_CRC32;
+      R.out_len = keep_prefix ? R.out_len : 0;
+    } else if (S.trailer_have < 2) R.status = TBZ_INPUT_UNDERRUN;  // gzip.lisp:96-99
+    else if (!size_only) R.flags |= 1;
   }
   ctx->tim.scan_ms = elapsed(ctx, 0, 1);
-  ctx->tim.find_ms = have_find ? elapsed(ctx, 8, 9) : 0.f;
-  ctx->tim.resolve_ms = have_resolve ? elapsed(ctx, 10, 11) : 0.f;
+  ctx->tim.find_ms = c.have_find ? elapsed(ctx, 8, 9) : 0.f;
+  ctx->tim.resolve_ms = ctx->tim.n_hgroups ? elapsed(ctx, 10, 11) : 0.f;  // (K6 ran)
   ctx->tim.lz_ms = elapsed(ctx, 4, 5) - ctx->tim.resolve_ms;
   ctx->tim.cksum_ms = elapsed(ctx, 5, 6);
   ctx->tim.total_ms = elapsed(ctx, 0, 6);
@@ -2139,6 +2112,32 @@ static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, co
             elapsed(ctx, 0, 1), elapsed(ctx, 1, 2), elapsed(ctx, 2, 3), elapsed(ctx, 3, 4), elapsed(ctx, 4, 5),
             elapsed(ctx, 5, 6));
   return 0;
+}
+
+// the whole pipeline on device-resident buffers
+static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, const uint64_t* in_offs,
+                        const uint64_t* in_lens, void* d_out, const uint64_t* out_offs, const uint64_t* out_caps,
+                        tbz_result* results, bool size_only, CoreOpts* opt = nullptr) {
+  Call c{ctx, format, n, d_in, in_offs, in_lens, d_out, out_offs, out_caps, results, size_only, opt};
+  bool done = false;
+  int r;
+  if ((r = call_begin(c, &done)) || done) return r;
+  if ((r = call_k0(c))) return r;          // stream table, markers and items (events 0 ..)
+  if ((r = call_k0b(c))) return r;         // block-start candidates (events 8 / 9)
+  if ((r = call_k0c(c))) return r;         // fixed-Huffman chains
+  if ((r = call_pools(c))) return r;       // (.. 1) token pools
+  if ((r = call_k1(c))) return r;          // the main launch (events 2 / 3), K3's verdict
+  if (c.simple) {
+    if ((r = call_device_layout(c))) return r;  // device layout + K2 (events 4 / 5)
+  } else {
+    std::vector<SegResult> res;  // the main launch's result per item
+    if ((r = call_host_results(c, res))) return r;
+    if ((r = call_chain_walk(c, res))) return r;  // + repair rounds
+    if ((r = call_distance(c))) return r;
+    if ((r = call_groups(c))) return r;
+    if ((r = call_host_k2(c))) return r;          // K2, K6 (events 4 / 5, 10 / 11)
+  }  // K4 / K5 (.. 6), trailer compare
+  return call_finish(c);
 }
 
 }  // namespace tbz
