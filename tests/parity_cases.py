@@ -4,6 +4,7 @@ Every case drives the product through the 3bz-shaped API (3bz_amd.api) and check
 oracle (oracle/tbz_oracle.c, itself pinned to the reference's vectors) on the same inputs:
 bit-exact octets, identical status flag, identical count, identical error class.
 """
+import functools
 import gzip as pygzip
 import hashlib
 import importlib
@@ -1441,26 +1442,603 @@ def multi_context_batch(engines):
         eng.free(d)
 
 
+# ---------------------------------------------------------------------------------- K2: match copies class by class
+# Hand-written streams (tools.corpus.MatchStream) aimed at the branches of k2_body / k2_resolve / k2_copy_coop: every
+# token is chosen here, the expected octets come from an octet-at-a-time LZ77 apply that _lz_apply and zlib agree with,
+# and every run asserts the kernel it went through.  One final block = one segment = one group: its output size alone
+# decides linear (<= K2_LINEAR_MAX) against ring.
+# The kernels' constants (tbz_kernels.hpp; tests/test_abi_and_host.py fails when this mirror is stale):
+K2R_HIST, K2R_FLUSH, K2R_SPAN = 8192, 2048, 1536
+K2R_RW = K2R_HIST + 2 * K2R_SPAN + 64    # the ring of the one-wave, two-wave and fused kernels
+K2R3_RW = K2R_HIST + 3 * K2R_SPAN + 64   # ... of the three-wave kernel
+K2_SHORT, K2_SMALL_MAX, K2_SLACK = 32, 32768, 64
+K2_LINEAR_MAX = K2_SMALL_MAX - K2_SLACK  # most octets of a group that takes the linear window
+SMALL_MAX_OUT = 256 << 10                # most octets the one-launch kernel (tbz_small_fused) produces
+
+
+def _first_diff(a, b):
+    return next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+
+
+def _k2_routed(eng, t, ring, what):
+    """the K2 kernel a general-path call of one group per stream went through (tbz_timings.k2_kinds: 1 dual, 2 small,
+    4 ring); `eng.flavour` is the test module's name for the engine's switches"""
+    if ring:
+        assert t.k2_kinds & 4 and not t.k2_kinds & 3, (what, t.k2_kinds)
+    else:
+        assert (t.k2_kinds & 7) == (2 if eng.flavour == "k2single" else 1), (what, eng.flavour, t.k2_kinds)
+
+
+def _k2_run(eng, s, p, what, caps=(), blocks=1):
+    """one hand-written stream: against the oracle, then alone through tbz_inflate (the engine's own flavour takes the
+    one-launch kernel, whose K2 is a ring whatever the size) and as a batch of two (the general path: linear or ring
+    by size), each with its route asserted; then with the buffer ending at `caps`.  `blocks`: how many blocks the stream
+    has (the finder, where it runs on every stream, may cut one of several blocks into several groups)"""
+    ring = len(p) > K2_LINEAR_MAX
+    w = assert_same(eng, s, "deflate", len(p), what=what)
+    assert w["flag"] == "finished" and w["bytes"] == p, what
+    fl = eng.flavour
+    if fl in ("auto", "k2ring2"):   # (the flavours that have the one-launch kernel; elsewhere the call above was this one)
+        out = bytearray(len(p))
+        r = eng.inflate(s, FMT["deflate"], out)
+        t = eng.timings()
+        assert r.status == 0 and r.out_len == len(p) and bytes(out) == p, (what, "alone", r.status, r.out_len, _first_diff(out, p))
+        if fl == "auto" and len(p) <= SMALL_MAX_OUT:
+            assert t.k2_kinds == 4 and t.k1_gang == 64 and t.huff_launches == 1, (what, t.k2_kinds, t.k1_gang, t.huff_launches)
+    o2 = [bytearray(len(p)), bytearray(len(p))]
+    r2 = eng.inflate_batch([s, s], FMT["deflate"], o2)
+    t = eng.timings()
+    for k in range(2):
+        assert r2[k].status == 0 and r2[k].out_len == len(p) and bytes(o2[k]) == p, (what, "batch", k, r2[k].status, _first_diff(o2[k], p))
+    if blocks == 1 or fl != "findalways":
+        _k2_routed(eng, t, ring, what)
+    for cap in caps:
+        assert_same(eng, s, "deflate", cap, what="%s, capacity %d" % (what, cap))
+
+
+def _k2_run_based(eng, s, p, what, bases=(0, 1, 7, 15)):
+    """the same stream through the device entry points with the output base moved by 0 / 1 / 7 / 15 octets (a0, the
+    window's alignment): alone, and all four as one batch"""
+    room = (len(p) + 64 + 15) & ~15
+    d_in, d_out = eng.malloc(len(s) + 64), eng.malloc(room * len(bases) + 64)
+    try:
+        eng.h2d(d_in, s)
+        for mis in bases:
+            r = eng.inflate_device(d_in, len(s), d_out + mis, len(p), FMT["deflate"])
+            got = bytearray(len(p))
+            eng.d2h(got, d_out + mis)
+            assert r.status == 0 and r.out_len == len(p) and bytes(got) == p, (what, "base", mis, r.status, _first_diff(got, p))
+        offs = [k * room + mis for k, mis in enumerate(bases)]
+        rs = eng.inflate_batch_device(d_in, [0] * len(bases), [len(s)] * len(bases), d_out, offs, [len(p)] * len(bases), FMT["deflate"])
+        _k2_routed(eng, eng.timings(), len(p) > K2_LINEAR_MAX, what)
+        whole = bytearray(room * len(bases))
+        eng.d2h(whole, d_out)
+        for r, o in zip(rs, offs):
+            assert r.status == 0 and r.out_len == len(p) and bytes(whole[o:o + len(p)]) == p, (what, "batch base", o & 15, _first_diff(whole[o:o + len(p)], p))
+    finally:
+        eng.free(d_in)
+        eng.free(d_out)
+
+
+_GRID_LENS = (3, 4, 5, 8, 9, 10, 16, 17, 18, 31, 32, 33, 34, 63, 64, 65, 127, 128, 129, 257, 258)
+_GRID_DISTS = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 258, 259, 1000)
+
+
+def _grid_pairs():
+    return [(ln, d) for ln in _GRID_LENS for d in sorted(set(_GRID_DISTS) | {ln - 1, ln, ln + 1})]
+
+
+def _grid_stream(pairs, seed, pad_to=None):
+    """~1100 aperiodic literals, then `pairs` with 0-3 literals before each (word parity of the head, its lane, rd and
+    rs mod 16 all vary); pad_to: filled up to exactly that many octets, the last token a match of 17..32 octets"""
+    rng = random.Random(seed)
+    m = K.MatchStream(seed)
+    m.begin(True)
+    m.lits(1100)
+    for ln, d in pairs:
+        m.lits(rng.randrange(4))
+        m.match(ln, d)
+    if pad_to is not None:
+        last = 17 + seed % 16
+        while pad_to - len(m.out) - last > 300:
+            m.lits(rng.randrange(1, 40))
+            m.match(rng.randrange(200, 259), rng.randrange(259, 1100))
+        m.lits(pad_to - len(m.out) - last)
+        m.match(last, 57)
+        assert len(m.out) == pad_to
+    return m.finish()
+
+
+@functools.lru_cache(None)
+def _grid_streams():
+    """(what, stream, plain): per shuffle the pairs in linear slices of 150 and all of them in one ring-sized block;
+    then the two sizes either side of the linear window's limit"""
+    pairs = _grid_pairs()
+    assert 480 <= len(pairs) <= 580, len(pairs)
+    res = []
+    for seed in (0x3B21, 0x3B22):
+        sh = list(pairs)
+        random.Random(seed).shuffle(sh)
+        for k in range(0, len(sh), 150):
+            s, p = _grid_stream(sh[k:k + 150], seed + k)
+            assert len(p) <= K2_LINEAR_MAX
+            res.append(("grid %x linear slice %d" % (seed, k // 150), s, p))
+        s, p = _grid_stream(sh, seed + 7)
+        assert len(p) > K2_LINEAR_MAX
+        res.append(("grid %x ring" % seed, s, p))
+    # every period a cooperative overlapping copy can have (k2_copy_coop takes j % dist through a float reciprocal, which is
+    # off by one at multiples of some distances — 41, 47, 55, 61 ... — and corrected): two periods and an octet of each
+    mod = [(min(258, 2 * d + 1), d) for d in range(K2_SHORT + 1, 258)]
+    for what, part in (("odd", mod[0::2]), ("even", mod[1::2]), ("all", mod)):
+        s, p = _grid_stream(part, 0x3B38 + len(part))
+        assert (len(p) > K2_LINEAR_MAX) == (what == "all"), len(p)
+        res.append(("cooperative periods, %s" % what, s, p))
+    for size in (K2_LINEAR_MAX, K2_LINEAR_MAX + 1):
+        s, p = _grid_stream(pairs[:60], 0x3B30 + size, pad_to=size)
+        res.append(("grid padded to %d" % size, s, p))
+    return tuple(res)
+
+
+def case_match_grid(eng):
+    """Every length class of the three fast paths (3 / 4-8 / 9-16 / 17-32, cooperative above K2_SHORT) against every
+    distance class (1 .. 1000, len - 1, len, len + 1: disjoint, touching, overlapping): ~550 pairs in two shuffles, in
+    linear slices and in one ring-sized block; a group of exactly K2_SMALL_MAX - K2_SLACK octets and of one more (the
+    linear window's sizing); the output base at 0 / 1 / 7 / 15 octets past a 16-octet line."""
+    streams = _grid_streams()
+    for what, s, p in streams:
+        _k2_run(eng, s, p, what)
+    for what, s, p in (streams[0], streams[4], streams[-2], streams[-1]):
+        _k2_run_based(eng, s, p, what)
+
+
+_RDY_LENS = (3, 8, 17, 32, 33, 258)
+
+
+def _readiness_pairs(m, rng, pairs_e):
+    """A, k literals, B: B's foreign source (what it does not write itself) ENDS at A's first octet + e where B is
+    disjoint; where B overlaps itself (its foreign source ends at its own first octet) it STARTS there"""
+    for la, lb, e, overlap in pairs_e:
+        k = rng.randrange(4)
+        m.lits(rng.randrange(3, 9))
+        if overlap:
+            dist = la + k - e            # source start = pos_B - dist = pos_A + e
+            while dist < 1:
+                k, dist = k + 1, dist + 1
+            if dist >= lb:
+                continue                 # (not an overlapping copy at this e)
+        else:
+            k = max(k, e - la)
+            dist = la + k + lb - e       # source end = pos_B - dist + len_B = pos_A + e
+        m.match(la, rng.randrange(40, 400))
+        m.lits(k)
+        m.match(lb, dist)
+
+
+def _chain(m, n, lens, gap):
+    """n matches of which each copies exactly what the one before produced (from its first octet on)"""
+    prev = lens[-1]
+    m.lits(prev)
+    for i in range(n):
+        m.lits(gap)
+        ln = lens[i % len(lens)]
+        m.match(ln, prev + gap)
+        prev = ln
+
+
+@functools.lru_cache(None)
+def _readiness_streams():
+    res = []
+    combos = [(la, lb, e, ov) for la in _RDY_LENS for lb in _RDY_LENS for e in (-1, 0, 1, la - 1, la, la + 1) for ov in (False, True)]
+    rng = random.Random(0x3B40)
+    rng.shuffle(combos)
+    for ring in (False, True):
+        parts = [combos] if ring else [combos[k:k + 110] for k in range(0, len(combos), 110)]
+        for k, part in enumerate(parts):
+            m = K.MatchStream(0x3B41 + k)
+            m.begin(True)
+            m.lits(600)
+            _readiness_pairs(m, rng, part)
+            s, p = m.finish()
+            assert (len(p) > K2_LINEAR_MAX) == ring, len(p)
+            res.append(("readiness pairs %s %d" % ("ring" if ring else "linear", k), s, p))
+    lens = (3, 8, 40, 17, 32, 33, 5, 258, 9, 64, 4, 31)
+    for n in (64, 65, 200):
+        for gap in (0, 1):
+            for lead in ((0,) if n < 200 else (0, 1, 2, 3)):   # (the batch's 128th word a head: whatever the parity before it)
+                m = K.MatchStream(0x3B50 + n + gap)
+                m.begin(True)
+                m.lits(100 + lead)
+                _chain(m, n, lens, gap)
+                s, p = m.finish()
+                res.append(("chain of %d, gap %d, lead %d" % (n, gap, lead), s, p))
+    m = K.MatchStream(0x3B58)   # the same chains behind a ring's worth of output
+    m.begin(True)
+    m.lits(9000)
+    while len(m.out) < 30_000:
+        m.lits(rng.randrange(3))
+        m.match(rng.randrange(100, 259), rng.randrange(300, 9000))
+    for n, gap in ((64, 0), (64, 1), (65, 0), (65, 1), (200, 0), (200, 1)):
+        m.lits(50 + gap)
+        _chain(m, n, lens, gap)
+    s, p = m.finish()
+    assert len(p) > K2_LINEAR_MAX
+    res.append(("chains in a ring group", s, p))
+    # a head in a batch's 128th word.  K1 writes the tokens in runs that it pads to whole granules of 8 words with
+    # no-ops, at places that depend on how it divided the bits among its lanes, so a token's word index cannot be set
+    # from here.  Where heads come every third word (head, distance, literal) a batch that begins on a literal has a
+    # head in its 128th word, takes 127 words and leaves the next one to begin on that head; that one ends on a distance
+    # word, and the one after begins on a literal again: between two paddings every other batch has its last head cut
+    # off from its distance, whatever the phase the padding left.  (Shown on the lane emulator when the case was
+    # written: with the words a lane accounts for wrong in that one place, `hb && !hbv`, both of these streams fail,
+    # alone and in a batch of two, and so do the readiness pairs, the chains of 64 and 65 without a gap, the chain of
+    # 200 behind 1 and 3 literals and the chains in a ring group: all of them have such a batch.)
+    for ring in (False, True):
+        m = K.MatchStream(0x3B5A + ring)
+        m.begin(True)
+        m.lits(40)
+        for i in range(10_000 if ring else 6_000):
+            m.match(3 + (i % 97 == 0) * (i % 200), 7 + i % 900)
+            m.lits(1)
+        s, p = m.finish()
+        assert (len(p) > K2_LINEAR_MAX) == ring, len(p)
+        res.append(("heads every third word, %s" % ("ring" if ring else "linear"), s, p))
+    # streams of exactly 127 / 128 / 129 token words (a literal is one word, a match two), ending on a match
+    for words in (127, 128, 129):
+        for nm in (1, 30):
+            m = K.MatchStream(0x3B60 + words)
+            m.begin(True)
+            m.lits(words - 2 * nm)
+            for i in range(nm):
+                m.match(3 + 5 * i, 1 + 3 * i)
+            s, p = m.finish()
+            res.append(("%d token words, %d matches" % (words, nm), s, p))
+    return tuple(res)
+
+
+def case_match_readiness(eng):
+    """The readiness rule (need <= hwm): B's source ending on / one octet into / at the end of / past the match before
+    it, short and cooperative matches becoming ready in the same round, dependency chains as deep as a batch and deeper
+    (64, 65, 200 links, with and without a literal between links: heads in word a and in word b), a head in the batch's
+    last word (its distance word opens the next batch), streams of 127 / 128 / 129 token words."""
+    for what, s, p in _readiness_streams():
+        _k2_run(eng, s, p, what)
+
+
+def k2_ring_class(pos, ln, dist, a0, rw):
+    """which path of k2_resolve / k2_copy_coop a match of a plain ring group takes (`rw`: the ring's size)"""
+    rd = (a0 + pos) % rw
+    rs = (rd - dist) % rw
+    if dist > K2R_HIST:
+        if ln > K2_SHORT:
+            return "far cooperative"
+        if rd + 32 > rw:
+            return "far at the seam"
+        return "far len >= 17" if ln >= 17 else "far wide"
+    if ln > K2_SHORT:
+        if dist < ln:
+            return "cooperative overlap"
+        return "cooperative seam" if rs + ln > rw or rd + ln > rw else "cooperative disjoint"
+    if dist < ln:
+        return "short overlap seam" if rs + 32 > rw or rd + 32 > rw else "short overlap"
+    return "in-ring seam" if rs + 32 > rw or rd + 32 > rw else "in-ring fast"
+
+
+_HIST_DISTS = (K2R_HIST - 1, K2R_HIST, K2R_HIST + 1, K2R_HIST + K2R_FLUSH - 1, K2R_HIST + K2R_FLUSH + 1, 32768)
+_HIST_LENS = (3, 4, 8, 9, 16, 17, 18, 32, 33, 258)
+# the sweep across the seam: a match's destination start, and separately its source start, at every window index from
+# RW + _SEAM_LO to RW + _SEAM_HI, for each of _SEAM_LENS, disjoint and overlapping (at the distance _SEAM_OVERLAP gives)
+_SEAM_LENS = (3, 9, 17, 33)
+_SEAM_LO, _SEAM_HI = -40, 8
+_SEAM_OVERLAP = {3: 2, 9: 4, 17: 11, 33: 20}
+# ... and the indices at which the kernel changes path: RW - 32 is the last start from which a 32-octet access stays
+# inside the ring (rs + 32 <= RW, rd + 32 <= RW), RW - 31 the first from which it does not; a cooperative copy of 33
+# octets fits from RW - 33 (rd + l <= RW) and not from RW - 32.  The sweep reaches these in its first _SEAM_EDGE_TURNS
+# turns, which is what a run on the lane emulator has time for
+_SEAM_EDGES = {3: (-32, -31), 9: (-32, -31), 17: (-32, -31), 33: (-33, -32)}
+_SEAM_EDGE_TURNS = 22
+
+
+def seam_targets(edges_only):
+    return {(end, i, ln, ov) for end in ("dst", "src") for ln in _SEAM_LENS for ov in (False, True)
+            for i in (_SEAM_EDGES[ln] if edges_only else range(_SEAM_LO, _SEAM_HI + 1))}
+
+
+@functools.lru_cache(None)
+def _seam_schedule():
+    """The sweep, turn by turn.  A match whose destination has to start at a given index takes its length of the ring's
+    turn, so a turn holds only a few of them: the matches are dealt to as many turns as it takes, those at _SEAM_EDGES
+    first, then the longest first, each into the first turn where it still fits.
+    -> per turn (placed, floating): placed = (destination start - seam, length, distance), floating = (source start -
+    seam, length) of disjoint matches that sit anywhere after the cluster"""
+    bound = []
+    for ln in _SEAM_LENS:
+        d = _SEAM_OVERLAP[ln]
+        for j in range(_SEAM_LO, _SEAM_HI + 1):          # disjoint, destination at j (its source somewhere in the ring)
+            bound.append((j not in _SEAM_EDGES[ln], -ln, j, 64 + (131 * (j - _SEAM_LO) + 17 * ln) % 1900))
+        for j in range(_SEAM_LO, _SEAM_HI + d + 1):      # overlapping: destination at j, source at j - d
+            bound.append((j not in _SEAM_EDGES[ln] and j - d not in _SEAM_EDGES[ln], -ln, j, d))
+    # a match of K2_SHORT octets itself, 31 octets before the seam: the one place where the 32 octets of a short copy's
+    # wide accesses are all its own and one of them is past the ring's end.  Destination there, in the ring and far
+    # (distance None), and source there
+    bound += [(False, -K2_SHORT, -31, 1500), (False, -K2_SHORT, -31, None), (False, -K2_SHORT, 9, 40)]
+    turns, pending = [], sorted(bound, key=lambda job: job[:3])
+    while pending:
+        # every fifth turn begins with a far match whose destination crosses the seam (distance None)
+        t = len(turns)
+        placed, rest = [] if t % 5 else [(-31 + 7 * t % 31, (3, 9, 17, 32)[t // 5 % 4], None)], []
+        for job in pending:
+            j, ln = job[2], -job[1]
+            if all(j + ln <= q[0] or q[0] + q[1] <= j for q in placed):
+                placed.append((j, ln, job[3]))
+            else:
+                rest.append(job)
+        turns.append(sorted(placed))
+        pending = rest
+    floating = sorted((i not in _SEAM_EDGES[ln], i, ln) for i in range(_SEAM_LO, _SEAM_HI + 1) for ln in _SEAM_LENS)
+    per = max(4, -(-len(floating) // len(turns)))
+    return tuple((tuple(t), tuple(f[1:] for f in floating[k * per:(k + 1) * per])) for k, t in enumerate(turns))
+
+
+RING_TURNS = len(_seam_schedule())   # the turns after which every target of the sweep has been met
+
+
+def _seam_offset(p, rw):
+    x = p % rw
+    return x - rw if x >= rw // 2 else x
+
+
+def seam_coverage(matches, a0, rw):
+    """the targets (seam_targets) that the in-ring matches of a stream meet"""
+    got = set()
+    for pos, ln, d in matches:
+        if d <= K2R_HIST:
+            got.add(("dst", _seam_offset(a0 + pos, rw), ln, d < ln))
+            got.add(("src", _seam_offset(a0 + pos - d, rw), ln, d < ln))
+    return got
+
+
+# at least this many matches of each class per stream of _SEAM_EDGE_TURNS turns and more, at every alignment of the
+# output's base (which moves the sweep by up to 15 indices).  By design: each turn has 4 to 6 matches of the sweep
+# whose destination starts within 40 octets of the seam, half of them overlapping, and 4 whose source does; every
+# fifth turn has the far match at the seam; the filler between seams draws the rest at the rates written there
+_RING_FLOORS = {"in-ring fast": 40, "in-ring seam": 16, "short overlap": 8, "short overlap seam": 6, "cooperative seam": 4,
+                "cooperative overlap": 8, "far wide": 12, "far len >= 17": 8, "far at the seam": 2, "far cooperative": 40}
+
+
+@functools.lru_cache(None)
+def _ring_stream(rw, wraps, seed, first=0, step=1):
+    """`wraps` turns of a ring of `rw` octets.  Between seams: far matches (distances just beyond K2R_HIST: sources
+    flushed as late as the kernel allows, at every phase of the flush interval) and the K2R_HIST grid.  Around every
+    seam a turn's share of the sweep (_seam_schedule, every `step`th turn from `first` on: with RING_TURNS turns all of it, with _SEAM_EDGE_TURNS the
+    indices where the kernel changes path) and, where it fits between them, a far match whose destination crosses the
+    seam.  -> (stream, plain, matches)"""
+    rng = random.Random(seed)
+    m = K.MatchStream(seed)
+    m.begin(True)
+    m.lits(K2R_HIST + 1100)
+    grid = [(ln, d) for d in _HIST_DISTS for ln in _HIST_LENS]
+    rng.shuffle(grid)
+    gi, schedule = 0, _seam_schedule()
+    for turn in range(1, wraps + 1):
+        seam = turn * rw
+        lo = seam + _SEAM_LO
+        while len(m.out) < lo:
+            left, kind = lo - len(m.out), rng.random()
+            if left < 3 or kind < 0.1:
+                m.lits(min(left, rng.randrange(1, 4)))
+                continue
+            if kind < 0.35 and gi < len(grid):            # the K2R_HIST grid
+                ln, d = grid[gi]
+                gi += 1
+                d = min(d, len(m.out))
+            elif kind < 0.5:                               # in the ring
+                ln = rng.choice((3, 5, 9, 17, 32, 33, 100))
+                d = rng.randrange(1, ln) if rng.random() < 0.4 else rng.randrange(1, K2R_HIST + 1)
+            else:                                          # far: flushed only just before, at every phase of the flush interval
+                ln = rng.choice((258, 258, 258, rng.randrange(3, 259)))
+                d = min(len(m.out), rng.choice((K2R_HIST + 1, K2R_HIST + 2, K2R_HIST + K2R_FLUSH, K2R_HIST + 259, 32768)))
+            m.match(min(ln, left), d)
+        placed, floating = schedule[(first + (turn - 1) * step) % len(schedule)]
+        for j, ln, d in placed:
+            m.lits(seam + j - len(m.out))
+            m.match(ln, d or _HIST_DISTS[2 + turn % 4])
+        m.lits(max(0, seam + _SEAM_HI + max(_SEAM_LENS) - len(m.out)))
+        for k, (i, ln) in enumerate(floating):             # disjoint, source at i
+            m.match(ln, len(m.out) - (seam + i))
+            m.lits((turn + k) & 1)
+    s, p = m.finish()
+    return s, p, tuple(m.matches)
+
+
+def _ring_census(matches, a0, rw):
+    c = {}
+    for pos, ln, d in matches:
+        k = k2_ring_class(pos, ln, d, a0, rw)
+        c[k] = c.get(k, 0) + 1
+    return c
+
+
+def case_ring_geometry(eng, wraps=_SEAM_EDGE_TURNS):
+    """Groups over K2_SMALL_MAX - K2_SLACK octets: distances either side of K2R_HIST (in-ring source against read-back
+    from the flushed output, the len >= 17 double load), destinations and sources across the ring's seam for both ring
+    sizes, buffers that end inside a short match, inside a cooperative one, on a flush boundary and one octet after the
+    first batch.  The stream's own census (k2_ring_class) holds a floor per class at every alignment of the output's
+    base, and its coverage of the sweep is asserted: every index from RW - 40 to RW + 8 with RING_TURNS turns (the
+    card), the indices where the kernel changes path (_SEAM_EDGES) with fewer (the lane emulator)."""
+    assert wraps >= _SEAM_EDGE_TURNS
+    want = seam_targets(wraps < RING_TURNS)
+    # (the whole sweep goes in two streams of a megabyte each, the schedule's even and odd turns: K1's narrower gangs
+    # hand larger streams on in pieces)
+    parts = ((0, wraps, 1),) if wraps < RING_TURNS else ((0, wraps - wraps // 2, 2), (1, wraps // 2, 2))
+    for rw in (K2R_RW, K2R3_RW):
+        met = set()
+        for first, n, step in parts:
+            what = "ring of %d, %d turns of the sweep from %d by %d" % (rw, n, first, step)
+            s, p, matches = _ring_stream(rw, n, 0x3B70 + (rw & 1023), first, step)
+            assert len(p) > K2_LINEAR_MAX
+            met |= seam_coverage(matches, 0, rw)
+            for a0 in (0, 1, 7, 15):
+                census = _ring_census(matches, a0, rw)
+                for k, floor in _RING_FLOORS.items():
+                    assert census.get(k, 0) >= floor, (what, a0, k, census)
+            short = next(x for x in matches if x[0] > 20_000 and x[1] <= 8)
+            coop = next(x for x in matches if x[0] > 25_000 and x[1] == 258)
+            caps = (short[0] + 1, coop[0] + 100, 10 * K2R_FLUSH, 128, 129)
+            _k2_run(eng, s, p, what, caps=caps)
+            _k2_run_based(eng, s, p, what, bases=(1, 15))
+        assert not want - met, (rw, wraps, len(want - met), sorted(want - met)[:8])
+
+
+_H_JOIN = 48 << 10   # a block that needs history joins the group before it while that group is smaller (tbz_engine.hpp)
+_OVERLAP_OPENERS = ((20, 5), (33, 7), (258, 100), (9, 1), (32, 31), (34, 33), (17, 16))
+
+
+def _symbolic_stream(n_blocks, lits_per_block, seed):
+    """`n_blocks` dynamic-Huffman blocks (the last one final) of _H_JOIN octets and more each, so that every block after
+    the first is an H-group of its own.  Each of them opens with matches whose source is placed relative to the block's
+    first octet B — an overlapping copy whose pattern begins before B, then sources before B, ending on it, across it —
+    and is filled up with literals and long matches that reach up to 32768 octets back.
+    -> (stream, plain, block offsets, offsets inside the matches at the blocks' starts)"""
+    rng = random.Random(seed)
+    m = K.MatchStream(seed, K.DynamicHuffmanWriter(*K.match_codes()))
+    inside, copied = [], None
+    for b in range(n_blocks):
+        m.begin(b == n_blocks - 1)
+        B = len(m.out)
+        if b:
+            def rel(ln, s):   # a match of ln octets whose source starts at B + s
+                m.match(ln, len(m.out) - (B + s))
+            ln, d = _OVERLAP_OPENERS[b % len(_OVERLAP_OPENERS)]
+            m.match(ln, d)                                 # overlapping straddler: the pattern is the d octets before B
+            inside.append(B + 2)
+            m.match(ln, ln + d - 1)                        # disjoint: the copy above and one octet from before B
+            rel(40, -10)
+            for ln in (3, 9, 17, 32, 33, 258):
+                rel(ln, -ln - 10)                          # wholly before B
+                rel(ln, -ln)                               # ends exactly on B
+                rel(ln, -ln + 1)                           # straddles B by one octet
+                rel(ln, -1)                                # ... by len - 1
+                m.lits(rng.randrange(3))
+            inside.append(len(m.out) - 100)
+            # pointer indices (32768 + s) & 255 = 247 .. 255: the carry in the mark plane's eight-octet runs
+            for ln in (3, 9, 17, 32):
+                for low in range(247, 256):
+                    rel(ln, low - 256 * rng.randrange(2, 100))
+            m.match(17, 32768)                             # distance 32768 exactly
+            m.match(258, 32768)
+            if copied is not None:                         # what the block before copied from the block before it
+                rel(copied[1], copied[0] - B)
+                rel(9, copied[0] - B + 3)
+        else:
+            m.lits(300)
+        step = lits_per_block // 16
+        for k in range(16):
+            m.lits(step)
+            if b and k == 8:
+                m.match(60, len(m.out) - (B - 200))        # mid-block, from before B: the next block's pointer of a pointer
+                copied = (len(m.out) - 60, 60)
+            while len(m.out) - B < (k + 1) * (_H_JOIN + 1500) // 16:
+                m.lits(rng.randrange(3))
+                m.match(rng.choice((258, 258, rng.randrange(3, 259))), rng.randrange(1, min(len(m.out), 32768) + 1))
+        m.end()
+    s, p = m.finish()
+    return s, p, tuple(m.blocks), tuple(inside)
+
+
+@functools.lru_cache(None)
+def _symbolic_streams(always):
+    # (TBZ_FIND=always searches every stream; the default finder takes streams of 48 KiB of input and more)
+    return _symbolic_stream(7, 2000 if always else 8000, 0x3B80)
+
+
+def case_symbolic_sources(eng):
+    """H-groups (both planes): blocks that the finder splits, each opening with matches whose source lies wholly before
+    the block's first octet, ends exactly on it, straddles it by 1 and by len - 1, overlaps itself across it, sits at
+    pointer indices whose low octet wraps inside the copy (k2_mark8's carry), or is 32768 octets back; blocks that copy
+    what the block before copied from the block before it (pointers of pointers, K6); then buffers that end inside
+    such matches."""
+    always = os.environ.get("TBZ_FIND") == "always" or getattr(eng, "flavour", None) == "findalways"
+    s, p, blocks, inside = _symbolic_streams(always)
+    what = "symbolic sources"
+    assert len(blocks) >= 7 and (always or len(s) >= 48 << 10), (len(blocks), len(s))
+    w = assert_same(eng, s, "deflate", len(p), what=what)
+    assert w["flag"] == "finished" and w["bytes"] == p
+    t = eng.timings()
+    assert t.n_hgroups >= len(blocks) - 2 and t.k2_kinds & 8, (what, t.n_hgroups, len(blocks), t.k2_kinds, t.n_candidates)
+    for cap in (inside[0], inside[5], blocks[3] + 1):
+        assert_same(eng, s, "deflate", cap, what="%s, capacity %d" % (what, cap))
+
+
+_STORED_RUNS = (1, 7, 8, 9, 63, 64, 65, 511, 512, 513, 3073)
+
+
+@functools.lru_cache(None)
+def _stored_streams():
+    res = []
+    for ring in (False, True):
+        rng = random.Random(0x3B90 + ring)
+        m = K.MatchStream(0x3B90 + ring)
+        m.begin()
+        m.lits(700)
+        while ring and len(m.out) < 29_000:
+            m.lits(rng.randrange(4))
+            m.match(rng.randrange(60, 259), rng.randrange(259, 700))
+        for n in _STORED_RUNS:
+            for _ in range(rng.randrange(20, 70)):         # a batch of matches; the last one ends on the run's doorstep
+                m.lits(rng.randrange(3))
+                m.match(rng.choice((3, 5, 9, 17, 32, 33, 70)), rng.randrange(1, 600))
+            m.match(rng.choice((4, 17, 40)), rng.randrange(1, 300))
+            m.end()
+            m.stored(n)
+            m.begin(n == _STORED_RUNS[-1])
+            m.match(3, 1)                                  # the run's last octet, twice its last two ...
+            m.match(4, 2) if n >= 2 else m.match(4, 1)
+            for ln in (3, 8, 17, 32):                      # ... its last 3 .. 32 (or whatever is before them)
+                m.match(ln, ln + rng.randrange(2))
+                m.lits(rng.randrange(2))
+            m.match(40, n + 57)                            # across the run: from the matches before it into it and beyond
+            m.match(258, n + 300)
+            m.match(20, min(n, 30) + 10)
+        m.lits(40)
+        s, p = m.finish()
+        assert (len(p) > K2_LINEAR_MAX) == ring, len(p)
+        res.append(("stored runs, %s" % ("ring" if ring else "linear"), s, p))
+    return tuple(res)
+
+
+def case_stored_run_neighbours(eng):
+    """Stored runs of 1 .. 3073 octets between batches of matches (the front end copies the run while the batch before
+    it is still being resolved): the last match before a run ends on its doorstep, the first ones after it read its
+    last 1 .. 32 octets and across it into the matches before; linear and ring."""
+    for what, s, p in _stored_streams():
+        _k2_run(eng, s, p, what, caps=(len(p) - 100, len(p) // 2), blocks=2 * len(_STORED_RUNS) + 1)
+
+
+K2_CASES = ["case_match_grid", "case_match_readiness", "case_ring_geometry", "case_symbolic_sources", "case_stored_run_neighbours"]
+
+
 ALL_CASES = [case_known_answer_vectors, case_test_deflated, case_reference_chunk_patterns, case_containers_and_levels, case_flush_streams,
              case_noflush_streams, case_block_starts_found, case_close_block_starts, case_fixed_block_chains, case_history_across_groups,
              case_configs_1_3_5, case_overflow_and_underrun, case_errors, case_false_markers, case_device_buffers,
              case_checksum_kernels, case_deep_codes, case_chunked_resume, case_gzip_members,
-             case_long_stored_runs, case_pointer_contexts, case_stream_contexts, case_container_headers, case_gzip_metadata, case_scratch_bounds, case_token_density, case_fuzz]
+             case_long_stored_runs, case_pointer_contexts, case_stream_contexts, case_container_headers, case_gzip_metadata, case_scratch_bounds, case_token_density, case_fuzz,
+             case_match_grid, case_match_readiness, case_ring_geometry, case_symbolic_sources, case_stored_run_neighbours]
 # what each engine flavour of the test modules runs.  "auto" runs everything; the others run the cases that can
 # tell them apart (the CPU suite has to stay within minutes: a case costs seconds on the lane emulator)
 FLAVOUR_CASES = {
     # K0b on every stream, however small: candidates, chains through false ones, symbolic history everywhere
     "findalways": ["case_known_answer_vectors", "case_containers_and_levels", "case_noflush_streams",
-                   "case_close_block_starts", "case_fixed_block_chains", "case_overflow_and_underrun", "case_false_markers", "case_errors", "case_fuzz"],
+                   "case_close_block_starts", "case_fixed_block_chains", "case_overflow_and_underrun", "case_false_markers", "case_errors", "case_fuzz",
+                   "case_match_grid", "case_match_readiness", "case_symbolic_sources"],
     # chain walk + layout on the host even where the device could (K3)
     "hostlayout": ["case_known_answer_vectors", "case_flush_streams", "case_configs_1_3_5",
-                   "case_false_markers", "case_device_buffers", "case_errors", "case_fuzz"],
+                   "case_false_markers", "case_device_buffers", "case_errors", "case_fuzz", "case_match_grid"],
     # one wave per group in K2
     "k2single": ["case_flush_streams", "case_history_across_groups", "case_configs_1_3_5", "case_deep_codes",
-                 "case_overflow_and_underrun"],
+                 "case_overflow_and_underrun"] + K2_CASES,
     # the ring kernel on two waves instead of three (large groups, H-groups)
     "k2ring2": ["case_noflush_streams", "case_history_across_groups", "case_configs_1_3_5", "case_containers_and_levels",
-                "case_long_stored_runs"],
+                "case_long_stored_runs"] + K2_CASES,
 }
 # the cases whose behaviour depends on the K1 flavour (forced-flavour runs skip the rest: checksums, device
 # buffers and the replay protocol go through the same engine calls whatever decodes the Huffman codes)

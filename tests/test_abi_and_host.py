@@ -69,3 +69,27 @@ def test_assign_streams_lpt():
     owner = M.assign_streams([800, 100, 100, 100, 100, 100, 100, 100, 100], 2)
     loads = [sum(s for s, o in zip([800] + [100] * 8, owner) if o == r) for r in range(2)]
     assert loads == [800, 800]
+
+
+def test_k2_constants_mirrored_by_the_parity_cases():
+    """tests/parity_cases.py aims its K2 streams at the kernels' constants (ring sizes, the history bound, the flush
+    interval, the linear window's limit): its mirror of them is read against tbz_kernels.hpp here"""
+    from tests import parity_cases as P
+    txt = open(os.path.join(ROOT, "3bz_amd", "csrc", "tbz_kernels.hpp")).read()
+
+    def default(name):   # #ifndef NAME / #define NAME value
+        return int(re.search(r"#ifndef %s\b.*\n#define %s (\d+)" % (name, name), txt).group(1))
+
+    def const(name):     # constexpr u32 NAME = expression;
+        return re.search(r"constexpr u32 %s = ([^;]+);" % name, txt).group(1).strip()
+    assert const("K2R_SPAN") == "TBZ_EXP_K2R_SPAN" and default("TBZ_EXP_K2R_SPAN") == P.K2R_SPAN
+    assert const("K2R_HIST") == "TBZ_EXP_K2R_HIST" and default("TBZ_EXP_K2R_HIST") == P.K2R_HIST
+    assert const("K2R_FLUSH") == "TBZ_EXP_K2R_FLUSH" and default("TBZ_EXP_K2R_FLUSH") == P.K2R_FLUSH
+    assert const("K2_SPAN") == "2 * K2R_SPAN" and const("K2R_RW") == "K2R_HIST + K2_SPAN + 64"
+    assert P.K2R_RW == P.K2R_HIST + 2 * P.K2R_SPAN + 64
+    assert const("K2R3_RW") == "K2R_HIST + 3 * K2R_SPAN + 64" and P.K2R3_RW == P.K2R_HIST + 3 * P.K2R_SPAN + 64
+    assert int(const("K2_SHORT")) == P.K2_SHORT and int(const("K2_SLACK")) == P.K2_SLACK
+    assert int(const("K2_SMALL_MAX")) == P.K2_SMALL_MAX and P.K2_LINEAR_MAX == P.K2_SMALL_MAX - P.K2_SLACK
+    assert const("SMALL_MAX_OUT") == "256u << 10" and P.SMALL_MAX_OUT == 256 << 10
+    # the ring kernels the mirror's two sizes stand for
+    assert re.search(r"using K2Ring = K2W<K2R_RW, K2R_HIST>;", txt) and re.search(r"using K2Ring3 = K2W<K2R3_RW, K2R_HIST>;", txt)

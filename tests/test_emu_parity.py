@@ -31,6 +31,7 @@ def eng(request):
     elif request.param != "auto":
         os.environ["TBZ_K1_MODE"] = request.param
     e = T.Engine(0, lib_path=os.path.join(EMU_DIR, "libtbz_emu.so"))
+    e.flavour = request.param  # (the K2 cases assert the kernels a call went through, which depend on it)
     os.environ.pop("TBZ_K1_MODE", None)
     os.environ.pop("TBZ_HOST_LAYOUT", None)
     os.environ.pop("TBZ_K2_MODE", None)

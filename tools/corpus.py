@@ -564,3 +564,106 @@ def full_size_corpora(jobs, workers=16):
     with ProcessPoolExecutor(max_workers=workers) as ex:
         res = list(ex.map(_full_job, [jobs[k] for k in names]))
     return dict(zip(names, res))
+
+
+# --------------------------------------------------------------------------- hand-written match streams
+# (tests/parity_cases.py, "K2: match copies class by class": every token is chosen, none is a compressor's)
+
+
+def lz_apply_octets(out, length, dist):
+    """RFC 1951 §3.2.3 as written: one octet at a time, no pattern-repeat shortcut (the plain reference that
+    _lz_apply's shortcut and zlib are checked against)"""
+    for _ in range(length):
+        out.append(out[-dist])
+
+
+def _bitrev(code, nbits):
+    r = 0
+    for i in range(nbits):
+        r |= ((code >> i) & 1) << (nbits - 1 - i)
+    return r
+
+
+_FIXED_LIT = [(_bitrev(0x30 + s, 8), 8) if s <= 143 else (_bitrev(0x190 + s - 144, 9), 9) for s in range(256)]
+
+
+def match_codes():
+    """complete dynamic codes under which every literal, length and distance can be written: literals 9 bits, the
+    end-of-block and length symbols 5 or 8, distances 4 or 5 (lit_lens, dist_lens for DynamicHuffmanWriter)"""
+    return [9] * 256 + [5] * 14 + [8] * 16, [4] * 2 + [5] * 28
+
+
+class MatchStream:
+    """One raw-deflate stream written token by token: fixed-Huffman blocks (or `writer`'s dynamic ones) and stored
+    blocks.  Literals come from an aperiodic filler (xorshift64*), so a source offset that is wrong by any amount
+    shows as a wrong octet.  `out` is the plaintext by lz_apply_octets; finish() checks it against _lz_apply and
+    zlib before anything else sees the stream.  `matches` = (offset, length, distance) of every match written."""
+
+    def __init__(self, seed, writer=None):
+        self.w = writer or FixedHuffmanWriter()
+        self.fixed = writer is None
+        self.out, self.chk = bytearray(), bytearray()
+        self.matches = []
+        self.blocks = []        # output offset of every Huffman block's first octet
+        self.open = False
+        self._seed, self._fill, self._fp = seed, b"", 0
+
+    def begin(self, final=False):
+        assert not self.open
+        self.w.begin_block(final)
+        self.blocks.append(len(self.out))
+        self.open = True
+
+    def end(self):
+        assert self.open
+        self.w.end_block()
+        self.open = False
+
+    def _take(self, n):
+        while self._fp + n > len(self._fill):
+            self._seed += 1
+            self._fill = self._fill[self._fp:] + xorshift64star_bytes(1 << 15, self._seed * 0x9E3779B97F4A7C15)
+            self._fp = 0
+        self._fp += n
+        return self._fill[self._fp - n:self._fp]
+
+    def lits(self, n):
+        assert self.open
+        data = self._take(n)
+        if self.fixed:
+            bits = self.w.bits
+            for c in data:
+                bits(*_FIXED_LIT[c])
+        else:
+            for c in data:
+                self.w.literal(c)
+        self.out += data
+        self.chk += data
+
+    def match(self, length, dist):
+        assert self.open and 3 <= length <= 258 and 1 <= dist <= min(len(self.out), 32768), (length, dist, len(self.out))
+        self.matches.append((len(self.out), length, dist))
+        self.w.match(length, dist)
+        lz_apply_octets(self.out, length, dist)
+        _lz_apply(self.chk, length, dist)
+
+    def stored(self, n, final=False):
+        """a stored block of n filler octets (between Huffman blocks)"""
+        assert not self.open and 0 <= n <= 65535
+        data = self._take(n)
+        self.w.bits(1 if final else 0, 3)
+        self.w.align()
+        self.w.buf += struct.pack("<HH", n, n ^ 0xFFFF) + data
+        self.out += data
+        self.chk += data
+
+    def finish(self):
+        """-> (stream, plain); the last block written must have been a final one"""
+        if self.open:
+            self.end()
+        self.w.align()
+        s, p = self.w.getvalue(), bytes(self.out)
+        assert p == bytes(self.chk), "octet-at-a-time apply and _lz_apply disagree"
+        d = zlib.decompressobj(-15)
+        assert d.decompress(s) == p and d.eof and not d.unused_data, "zlib disagrees with the hand-written stream"
+        return s, p
