@@ -180,7 +180,7 @@ struct tbz_ctx {
   size_t pipe_part = 32u << 20; // ... of about this many input octets (env TBZ_PIPE_PART_KIB)
   int copy_threads = 8;      // env TBZ_COPY_THREADS (1: the calling thread alone)
   size_t stage_chunk = 16u << 20;  // env TBZ_STAGE_CHUNK_KIB
-  int k1_mode = 0;  // 0 auto, 1 lane-per-item, 4..64 gang of that many lanes (env TBZ_K1_MODE; tests force each)
+  int k1_mode = 0;  // 0 auto, 1 lane-per-item, 8..64 gang of that many lanes (env TBZ_K1_MODE; tests force each)
   bool sym_hist = true;  // groups that need history they do not hold run against symbolic history + K6 (env TBZ_HIST=off:
                          // they join their predecessors' group instead, one workgroup per chain, as in round 1)
   uint64_t pool_cap = 96ull << 30;  // octets of token pool + run tables one pass may hold (env TBZ_POOL_CAP_MIB): a batch
@@ -2170,6 +2170,7 @@ const char* tbz_strerror(int code) {
     case TBZ_E_GZIP_FLAGS: return "reserved gzip flag bits set";
     case TBZ_E_GZIP_HCRC: return "gzip header crc mismatch";
     case TBZ_E_CRC32: return "crc32 mismatch";
+    case TBZ_E_TREE_OVERFLOW: return "huffman table too large for the tree";
     case TBZ_E_ARG: return "bad argument";
     case TBZ_E_HIP: return "HIP runtime error";
     case TBZ_E_NOMEM: return "out of device memory";
@@ -2189,6 +2190,13 @@ int tbz_device_count(void) {
 int tbz_ctx_create(int device_id, tbz_ctx** out_ctx) {
   if (!out_ctx) return TBZ_E_ARG;
   *out_ctx = nullptr;
+  // TBZ_K1_MODE names a K1 flavour or is not set: a value that names none is an error
+  int k1_mode = 0;
+  if (const char* m = getenv("TBZ_K1_MODE")) {
+    if (!strcmp(m, "lane")) k1_mode = 1;
+    else if (!strcmp(m, "gang8") || !strcmp(m, "gang16") || !strcmp(m, "gang32") || !strcmp(m, "gang64")) k1_mode = atoi(m + 4);
+    else if (*m) return TBZ_E_ARG;
+  }
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return TBZ_E_NO_DEVICE;
   if (device_id < 0 || device_id >= n) return TBZ_E_ARG;
@@ -2249,13 +2257,7 @@ int tbz_ctx_create(int device_id, tbz_ctx** out_ctx) {
   if (const char* m = getenv("TBZ_HIST")) ctx->sym_hist = strcmp(m, "off") != 0;
   if (const char* m = getenv("TBZ_POOL_CAP_MIB")) ctx->pool_cap = (uint64_t)std::max(1, atoi(m)) << 20;
   if (const char* m = getenv("TBZ_FIND")) ctx->find_mode = !strcmp(m, "off") ? 0 : !strcmp(m, "always") ? 2 : 1;
-  if (const char* m = getenv("TBZ_K1_MODE")) {
-    if (!strcmp(m, "lane")) ctx->k1_mode = 1;
-    else if (!strncmp(m, "gang", 4)) {
-      int g = atoi(m + 4);
-      if (g == 8 || g == 16 || g == 32 || g == 64) ctx->k1_mode = g;
-    }
-  }
+  ctx->k1_mode = k1_mode;
   *out_ctx = ctx;
   return 0;
 }

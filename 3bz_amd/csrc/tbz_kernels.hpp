@@ -36,7 +36,7 @@ namespace tbz {
 // ------------------------------------------------------------------------------------------------
 constexpr i32 E_BTYPE = -1, E_STORED_LEN = -2, E_OVERSUB = -3, E_INCOMPLETE = -4, E_REPEAT_NO_PREV = -5,
               E_REPEAT_OVERRUN = -6, E_INVALID_CODE = -7, E_ZLIB_HEADER = -9, E_ZLIB_DICT = -10,
-              E_GZIP_MAGIC = -12, E_GZIP_METHOD = -13, E_GZIP_FLAGS = -14, E_GZIP_HCRC = -15;
+              E_GZIP_MAGIC = -12, E_GZIP_METHOD = -13, E_GZIP_FLAGS = -14, E_GZIP_HCRC = -15, E_TREE_OVERFLOW = -18;
 
 // ------------------------------------------------------------------------------------------------
 // small wave helpers
@@ -1314,6 +1314,11 @@ TBZ_DEV i32 build_canon(const u8* lens, u32 n, u16 (*tmp)[64], const CanonStore&
     off += c;
   }
   if (!err && left > 0 && used > 1) err = E_INCOMPLETE;
+  // one code alone, 11 bits or longer: the reference's root table of 2^length entries does not fit its node array
+  // (huffman-tree.lisp:213-217 against constants.lisp:4-7) and the build fails.  Only this shape is mirrored here: the
+  // array's other bounds (nested sub-tables past 1444 entries in all, one starting past entry 1023) are the oracle's
+  // to report, and no stream of the suite reaches them, the deepest codes of case_code_tables included
+  if (!err && used == 1 && cn.min_len > 10) err = E_TREE_OVERFLOW;
   if (err) return err;
   if (cs.bit8)
     for (u32 k = 0; k < cs.cap / 32; k++) cs.bit8[k][lane] = 0;
@@ -2188,6 +2193,7 @@ TBZ_DEV i32 kg_build(const u8* lens, u32 n, SymT* sorted, u32* lim, u16* dlt, u1
   }
   if (leader && n) lim[15] = min_len;
   if (!err && left > 0 && used > 1) err = E_INCOMPLETE;
+  if (!err && used == 1 && min_len > 10) err = E_TREE_OVERFLOW;  // (as build_canon: huffman-tree.lisp:213-217)
   const bool ok = n != 0 && err == 0;
   // 4. canonical order: slot = first slot of the length + same-length symbols before this one
   u32 nxt[8];

@@ -56,6 +56,8 @@ enum {
   TBZ_E_GZIP_FLAGS = -14,    /* gzip.lisp:133-134 */
   TBZ_E_GZIP_HCRC = -15,     /* gzip.lisp:255 */
   TBZ_E_CRC32 = -16,         /* gzip.lisp:93 */
+  TBZ_E_TREE_OVERFLOW = -18, /* a single code of 11 bits or more: the root table of 2^length entries overruns the node
+                                array, huffman-tree.lisp:213-217 with constants.lisp:4-7 */
   /* engine failures (also used as function return codes) */
   TBZ_E_ARG = -100,
   TBZ_E_HIP = -101,     /* a HIP runtime call failed; tbz_last_error(ctx) has the text */

@@ -4,6 +4,7 @@ Every case drives the product through the 3bz-shaped API (3bz_amd.api) and check
 oracle (oracle/tbz_oracle.c, itself pinned to the reference's vectors) on the same inputs:
 bit-exact octets, identical status flag, identical count, identical error class.
 """
+import contextlib
 import functools
 import gzip as pygzip
 import hashlib
@@ -424,7 +425,7 @@ def case_token_density(eng):
         e2 = T.Engine(eng.device, lib_path=eng.lib._name)
     finally:
         os.environ.pop("TBZ_TOK_FULL", None)
-    os.environ["TBZ_K1_MODE"] = "32"  # a forced flavour hands what it declines straight to the one-lane kernel
+    os.environ["TBZ_K1_MODE"] = "gang32"  # a forced flavour hands what it declines straight to the one-lane kernel
     try:
         e3 = T.Engine(eng.device, lib_path=eng.lib._name)
     finally:
@@ -437,6 +438,7 @@ def case_token_density(eng):
             assert w2["bytes"] == w["bytes"]
             if k in (0, 2, 4):
                 assert_same(e3, data, fmt, n, what=what + " [gangs of 32]")
+                assert e3.timings().k1_gang == 32, (what, e3.timings().k1_gang)
             assert_same(eng, data, fmt, n // 2, what=what + ", short buffer")
             assert_same(eng, data, fmt, n, end=len(data) * 2 // 3, what=what + ", cut")
         # the zeros went through the second launch (regions of their own), not through a pool of one word per bit
@@ -2014,6 +2016,708 @@ def case_stored_run_neighbours(eng):
         _k2_run(eng, s, p, what, caps=(len(p) - 100, len(p) // 2), blocks=2 * len(_STORED_RUNS) + 1)
 
 
+# ---------------------------------------------------------------------------------- K1: headers, code tables, tokens
+# Hand-written dynamic blocks (tools.corpus.DynamicBlockWriter: every header field explicit) aimed at the separate
+# implementations of one grammar: k1_dynamic_header / build_canon / canon_decode (the one-lane kernel, and K1h for an
+# item's first block), kg_dynamic_header (fast pass and exact loop: every other header), kg_build (two-level tables,
+# pools per gang width), kg_span / kg_exact_step.  Every stream goes through every route of k1_routes() and a second
+# time behind a non-final block; everything is compared with the oracle to the bit (flag, count, octets, error).
+# The kernels' constants (tbz_kernels.hpp; tests/test_abi_and_host.py fails when this mirror is stale):
+KG_TBL, KG_TBD = 9, 8                    # index bits of the first-level tables
+KG_POOLS = {"lit": 352, "dist": 128, "lit32": 288, "dist32": 64}   # second-level entries (gangs of 32: the smaller ones)
+E_OVERSUB, E_INCOMPLETE, E_NO_PREV, E_OVERRUN, E_INVALID, E_TREE = -3, -4, -5, -6, -7, -18
+
+
+def _fused_route(t, n):
+    return t.k1_gang == 64 and t.huff_launches == 1 and t.scan_ms == 0.0
+
+
+def _auto_gangs(t, n):
+    """the engine's own choice without the one-launch path: gangs of 8 up to 3 072 bits a lane, wider ones from there on
+    (k1_gang, tbz_engine.hpp) - never one lane per item"""
+    return t.k1_gang == 8 if n * 8 <= 8 * 3072 else t.k1_gang in (8, 16, 32, 64)
+
+
+@contextlib.contextmanager
+def k1_routes(eng, gang32=False):
+    """the engines a stream must pass for the fixture engine `eng`, as (name, engine, check of timings() after a clean
+    call of so many octets): `auto` - the engine itself (one small stream: tbz_small_fused, gangs of 64, no K1h), K1h +
+    gangs of 8 (TBZ_SMALL_FUSED=0) and gangs of 8 whose leaders parse every header (TBZ_K1H=0 too); a forced gang width - itself
+    and without K1h; `lane`, `findalways` - the engine itself.  gang32: the default flavour gets an engine of gangs of 32
+    as well (the gang width with pools of its own; the lane emulator's suite has no such flavour)."""
+    fl = getattr(eng, "flavour", "auto")
+    extra = []
+
+    def make(env):
+        os.environ.update(env)
+        try:
+            e = T.Engine(eng.device, lib_path=eng.lib._name)
+        finally:
+            for k in env:
+                os.environ.pop(k, None)
+        extra.append(e)
+        return e
+    try:
+        if fl == "auto":
+            routes = [("fused", eng, _fused_route),
+                      ("K1h + gangs of 8", make({"TBZ_SMALL_FUSED": "0"}), _auto_gangs),
+                      ("gangs of 8, no K1h", make({"TBZ_SMALL_FUSED": "0", "TBZ_K1H": "0"}), _auto_gangs)]
+            if gang32:
+                routes.append(("gangs of 32", make({"TBZ_K1_MODE": "gang32"}), lambda t, n: t.k1_gang == 32))
+        elif fl.startswith("gang"):
+            g = int(fl[4:])
+            routes = [(fl, eng, lambda t, n: t.k1_gang == g),
+                      (fl + ", no K1h", make({"TBZ_K1_MODE": fl, "TBZ_K1H": "0"}), lambda t, n: t.k1_gang == g)]
+        elif fl == "lane":
+            routes = [(fl, eng, lambda t, n: t.k1_gang == 1)]
+        else:
+            routes = [(fl, eng, lambda t, n: t.k1_gang in (1, 8, 16, 32, 64))]
+        yield routes
+    finally:
+        for e in extra:
+            e.close()
+
+
+_STATUS = {"finished": 0, "underrun": 1, "overflow": 2}
+
+
+def _k1_run(routes, s, cap, what, plain=None, end=None, stale=False):
+    """one stream on every route, through the state API against the oracle (same_or_stale_tables), with the route asserted
+    where the stream is clean; the one-launch path is not behind the state API, so that route's engine decodes the
+    stream through tbz_inflate as well, against the same oracle result.  `plain`: what the writer predicts (the stream
+    must then finish with exactly that).  `stale`: the stream has, or being damaged may have, an all-zero alphabet - only
+    then is the documented deviation of same_or_stale_tables allowed; every other stream must agree with the oracle as
+    it is."""
+    data = s if end is None else s[:end]
+    for name, e, routed in routes:
+        if stale:
+            w, dev = same_or_stale_tables(e, data, "deflate", cap, what="%s [%s]" % (what, name))
+        else:
+            w, dev = assert_same(e, data, "deflate", cap, what="%s [%s]" % (what, name)), False
+        if plain is not None:
+            assert w["flag"] == "finished" and w["bytes"] == plain and not dev, (what, name, w["flag"], w["code"])
+        if routed is not _fused_route:
+            t = e.timings()
+            assert w["flag"] != "finished" or routed(t, len(data)), (what, name, "route", t.k1_gang)
+            continue
+        if not data:
+            continue
+        out = bytearray(cap)
+        r = e.inflate(data, FMT["deflate"], out)
+        t = e.timings()
+        want = _STATUS.get(w["flag"], w["code"])
+        assert r.status == want, (what, name, "tbz_inflate", r.status, want)
+        if w["flag"] != "error":
+            assert r.out_len == w["offset"] and bytes(out[:r.out_len]) == w["bytes"], (what, name, "tbz_inflate", r.out_len, w["offset"], _first_diff(out, w["bytes"]))
+        # (a stream that holds a flush marker's octets, here by chance of its header's bits, is the general path's)
+        if w["flag"] == "finished" and b"\x00\x00\xff\xff" not in data:
+            assert routed(t, len(data)), (what, name, "route", t.k1_gang, t.huff_launches, t.scan_ms)
+    return w
+
+
+_PREFIXES = (None, "stored") + tuple(range(8))
+
+
+def _prefixed(build, prefix):
+    """the stream `build(w)` writes, behind nothing, a non-final stored block, or a non-final fixed block of k literals
+    >= 144 (10 + 9 k bits: k = 0..7 puts the next header at each of the eight bit phases of an octet) - behind a block
+    the header is not its item's first, which the gang leader parses even with K1h on.
+    -> (stream, plain, header spans)"""
+    w = K.DynamicBlockWriter()
+    if prefix == "stored":
+        w.stored(K.xorshift64star_bytes(37, 0x3BA0))
+    elif prefix is not None:
+        w.fixed_literals(bytes(144 + 13 * i for i in range(prefix)))
+    build(w)
+    s, p = w.finish()
+    return s, p, w.spans
+
+
+def _use_all(w, n_tokens, seed, final=True):
+    """one block under w's codes that uses every coded literal, length symbol (257..285) and distance symbol (0..29) at
+    least once - far distances as soon as the output is long enough for them, the longest length while it is not - and
+    has n_tokens tokens or more"""
+    rng = random.Random(seed)
+    lits = [c for c in range(256) if w.lit_lens[c]]
+    lsyms = [c for c in range(257, min(286, len(w.lit_lens))) if w.lit_lens[c]]
+    dsyms = [c for c in range(min(30, len(w.dist_lens))) if w.dist_lens[c]]
+    w.begin_block(final)
+    n = 0
+    for c in lits:
+        w.literal(c)
+        n += 1
+    if lsyms and dsyms and w.out:
+        todo_l, todo_d = list(lsyms), list(dsyms)
+        while todo_l or todo_d or n < n_tokens:
+            n += 1
+            if lits and not (todo_l or todo_d) and rng.random() < 0.6:
+                w.literal(rng.choice(lits))
+                continue
+            feas = [d for d in dsyms if K._DIST_BASE[d] <= len(w.out)]
+            waiting = bool(todo_d) and todo_d[0] not in feas
+            if todo_d and not waiting:
+                d = todo_d.pop(0)
+            else:
+                d = rng.choice(feas)
+            ls = lsyms[-1] if waiting else todo_l.pop() if todo_l else rng.choice(lsyms)
+            lx = rng.choice((0, (1 << K._LEN_EXTRA[ls - 257]) - 1))
+            dx_max = min((1 << K._DIST_EXTRA[d]) - 1, len(w.out) - K._DIST_BASE[d], 32768 - K._DIST_BASE[d])
+            w.match_syms(ls, lx, d, rng.choice((0, dx_max, rng.randrange(dx_max + 1))))
+    else:
+        while lits and n < n_tokens:
+            w.literal(rng.choice(lits))
+            n += 1
+    if w.lit_lens[256]:
+        w.end_block()
+
+
+def _spread(lengths, symbols, size):
+    """a length list of `size` entries with `lengths` on `symbols` (as many as there are lengths), zero elsewhere"""
+    assert len(lengths) <= len(symbols), (len(lengths), len(symbols))
+    out = [0] * size
+    for l, c in zip(lengths, symbols):
+        out[c] = l
+    return out
+
+
+_HG_LITS = tuple(range(97, 123))
+
+
+def _hg_lit(hlit=286, extra=(257, 264, 285), n=16, length=4):
+    """the grammar streams' usual literal/length code: end-of-block, the symbols in `extra` and literals from 'a' on,
+    n codes of `length` bits (complete for n = 2^length)"""
+    syms = list(dict.fromkeys([256] + [c for c in extra if 256 < c < hlit]))
+    syms += _HG_LITS[:n - len(syms)]
+    return _spread([length] * n, syms, hlit)
+
+
+_HG_DIST = [2, 2, 0, 0, 2, 0, 0, 0, 0, 0, 2]       # distance symbols 0, 1, 4 and 10
+
+
+def _zero_run(n, first=None):
+    """(symbol, extra) pairs for n zeros, `first` being the first pair sent"""
+    if first is None:
+        return K.cl_rle([0] * n)
+    k = len(K.cl_expand([first]))
+    assert k <= n
+    return [first] + K.cl_rle([0] * (n - k))
+
+
+def _cl_code(pairs, also=()):
+    """a complete code-length code over the symbols in `pairs` (and `also`); one symbol alone gets a 1-bit code"""
+    used = sorted({s for s, _ in pairs if s != "raw"} | set(also))
+    return _spread(K.complete_lengths(len(used)), used, 19)
+
+
+class _Hdr:
+    """one grammar stream: how to write it; whether RFC 1951 allows it (True: zlib must agree with the writer's plaintext
+    and every route must finish with it; "ref": the reference takes it, zlib does not - HLIT over 286, HDIST over 30);
+    the error the reference gives where it is known by construction; and whether it has an all-zero alphabet (`stale`:
+    the one kind of stream that may take the documented deviation of same_or_stale_tables)"""
+
+    def __init__(self, name, build, valid=False, code=None, stale=False):
+        self.name, self.build, self.valid, self.code, self.stale = name, build, valid, code, stale
+
+
+def _hdr(name, valid=False, code=None, body=None, n_tokens=40, stale=False, **kw):
+    """a stream of one final dynamic block: DynamicBlockWriter.codes(**kw), then `body(w)` (default: _use_all)"""
+    def build(w):
+        w.codes(**kw)
+        if body is None:
+            _use_all(w, n_tokens, len(name))
+        else:
+            w.begin_block(True)
+            body(w)
+    return _Hdr(name, build, valid, code, stale)
+
+
+def _from_pairs(name, pairs, hlit, valid=False, code=None, body=None, cl_lens=K.CL_FLAT, **kw):
+    """... whose code lengths are what `pairs` expand to (hlit of them literal/length), or, where the pairs mean nothing,
+    a header alone"""
+    lens = K.cl_expand([p for p in pairs if p[0] != "raw"])
+    if valid:
+        assert lens is not None and len(lens) > hlit, name
+        return _hdr(name, valid, code, body, lit_lens=lens[:hlit], dist_lens=lens[hlit:], cl_syms=pairs, cl_lens=cl_lens, **kw)
+    kw.setdefault("hlit_field", hlit - 257)
+    kw.setdefault("hdist_field", 3)
+    return _hdr(name, False, code, (lambda w: w.bits(0x5A5A5A, 24)) if body is None else body, lit_lens=_hg_lit(), dist_lens=_HG_DIST,
+                cl_syms=pairs, cl_lens=cl_lens, **kw)
+
+
+def _lit_pairs(first_zero, n_lits=14):
+    """pairs for 258 literal/length lengths: zeros sent with `first_zero` first, n_lits literals of 4 bits, zeros up to
+    the end-of-block symbol, which has 4 bits like symbol 257"""
+    z = len(K.cl_expand([first_zero]))
+    return _zero_run(z, first_zero) + [(4, 0)] * n_lits + _zero_run(256 - z - n_lits) + [(4, 0), (4, 0)]
+
+
+_DIST4 = [(2, 0)] * 4            # four 2-bit distance codes
+
+
+def _hclen_streams():
+    """every HCLEN 4..19 with a non-zero length on the last entry sent.  With 4 entries (16, 17, 18, 0) no length but
+    zero can be sent: all-zero alphabets.  From 5 on the last entry is a length L: a complete literal code that has it
+    (L < 8: one code of L bits and 8-bit codes; L = 8: 256 8-bit codes; L > 8: 127 7-bit codes, one each of 8 .. L - 1
+    bits, two of L), no distance code (what zlib sends for literals alone)."""
+    res = []
+    pairs = _zero_run(257) + [(0, 0)]
+    res.append(_from_pairs("HCLEN 4", pairs, 257, cl_lens=_spread([1, 1], [0, 18], 19), hclen=4, hdist_field=0, stale=True))
+    for h in range(5, 20):
+        L = K.CL_ORDER[h - 1]
+        ls = [L] + [8] * (256 - (1 << (8 - L))) if L < 8 else [8] * 256 if L == 8 else [L, L] + list(range(L - 1, 7, -1)) + [7] * 127
+        lit = _spread(ls, [256] + list(range(97, 256)) + list(range(97)), 257)
+        pairs = K.cl_plain(lit + [0])
+        cl = _cl_code(pairs)
+        assert all(c in K.CL_ORDER[:h] for c in range(19) if cl[c]) and cl[L]
+        res.append(_hdr("HCLEN %d" % h, True, lit_lens=lit, dist_lens=[0], cl_lens=cl, hclen=h, cl_syms=pairs, n_tokens=300))
+    return res
+
+
+def _cl_shape_streams():
+    res = []
+    flat = dict(lit_lens=_hg_lit(), dist_lens=[4] * 16)
+    res.append(_hdr("code-length code: two 1-bit codes", True, cl_lens=_spread([1, 1], [0, 4], 19), **flat))
+    # 3,3,3,3 2 4 5 5 on 'a'..'h', 3 on end-of-block; four 2-bit distance codes and a zero: 18, 17, 16, 0, 2, 3, 4, 5 all sent
+    deep = ([(18, 86), (3, 0), (16, 0), (2, 0), (4, 0), (5, 0), (5, 0), (18, 127), (17, 7), (17, 0), (3, 0)] +
+            [(2, 0), (16, 0), (0, 0)])
+    res.append(_from_pairs("code-length code: 1,2,3,4,5,6,7,7", deep, 257, True,
+                           cl_lens=_spread([1, 2, 3, 4, 5, 6, 7, 7], [3, 2, 16, 5, 18, 17, 4, 0], 19)))
+    for L in (1, 7):
+        one = _spread([L], [8], 19)
+        res.append(_from_pairs("one code-length code of %d bits: 258 eights" % L, [(8, 0)] * 258, 257, code=E_OVERSUB, cl_lens=one, hdist_field=0))
+        z18 = _spread([L], [18], 19)
+        res.append(_from_pairs("one code-length code of %d bits: zeros by 18" % L, [(18, 127), (18, 109)], 257, cl_lens=z18, hdist_field=0, stale=True))
+        for at in (0, 100):   # the unassigned pattern: first, and after a hundred symbols (L = 7: in its first and its last bit)
+            for pat in ((1,), (1, 1 << 6))[L == 7]:
+                bad = [(8, 0)] * at + [("raw", (pat, L))] + [(8, 0)] * 8
+                res.append(_from_pairs("one code-length code of %d bits, pattern %d unassigned at %d" % (L, pat, at), bad, 257, code=E_INVALID,
+                                       cl_lens=one, hdist_field=0))
+    lens258 = K.cl_plain(_hg_lit(257, ()) + [0])
+    res.append(_from_pairs("code-length code over-subscribed at 1 bit", lens258, 257, code=E_OVERSUB, cl_lens=_spread([1, 1, 1], [0, 4, 5], 19), hdist_field=0))
+    res.append(_from_pairs("code-length code over-subscribed at 7 bits", lens258, 257, code=E_OVERSUB,
+                           cl_lens=_spread([1, 2, 3, 4, 5, 6, 7, 7, 7], [0, 4, 1, 2, 3, 5, 6, 7, 8], 19), hdist_field=0))
+    res.append(_from_pairs("code-length code incomplete, two codes", lens258, 257, code=E_INCOMPLETE, cl_lens=_spread([1, 2], [0, 4], 19), hdist_field=0))
+    res.append(_from_pairs("code-length code incomplete, 2 2 2", lens258, 257, code=E_INCOMPLETE, cl_lens=_spread([2, 2, 2], [0, 4, 5], 19), hdist_field=0))
+    for h in (4, 19):   # all zero: the reference keeps its previous code-length table (the documented deviation)
+        res.append(_hdr("code-length code all zero, HCLEN %d" % h, body=lambda w: w.bits(0x3B3B3B, 24), lit_lens=_hg_lit(), dist_lens=_HG_DIST,
+                        cl_lens=[0] * 19, hclen=h, cl_syms=[], stale=True))
+    return res
+
+
+def _repeat_streams():
+    res = []
+    for x in range(4):    # 16: three to six copies
+        pairs = _zero_run(97) + [(4, 0), (16, x)] + [(4, 0)] * (10 - x) + _zero_run(256 - 111) + [(4, 0), (4, 0)] + _DIST4
+        res.append(_from_pairs("16 with extra %d" % x, pairs, 258, True))
+    for first in ((17, 0), (17, 7), (18, 0), (18, 1), (18, 126), (18, 127)):
+        res.append(_from_pairs("%d with extra %d" % first, _lit_pairs(first) + _DIST4, 258, True))
+    res.append(_from_pairs("16 as the very first symbol", [(16, 0)] + _lit_pairs((18, 0))[1:] + _DIST4, 258, code=E_NO_PREV))
+    for first in ((17, 0), (18, 0), (18, 127)):   # 16 after 17 / 18 repeats the zero: as the first two symbols, and
+        for x in (0, 3):                          # behind a length that is not zero (which must not be what is repeated)
+            for lead in (0, 1):
+                z = lead + len(K.cl_expand([first])) + 3 + x
+                pairs = [(4, 0)] * lead + [first, (16, x)] + [(4, 0)] * (14 - lead) + _zero_run(256 - z - 14 + lead) + [(4, 0), (4, 0)] + _DIST4
+                res.append(_from_pairs("16 (extra %d) directly after %d (extra %d)%s" % ((x,) + first + (", a length before them" * lead,)),
+                                       pairs, 258, True))
+    lit258 = _lit_pairs((18, 127))
+    # 16 as the first symbol of the distance part: it carries the last literal/length length (sixteen 4-bit distance codes)
+    res.append(_from_pairs("16 as the first distance symbol", lit258 + [(16, 3), (16, 3), (16, 1)], 258, True))
+    # ... straddling HLIT: symbol 258 and the first two distance codes
+    pairs = _lit_pairs((18, 127), 13) + [(16, 0), (16, 3), (16, 3), (4, 0), (4, 0)]
+    res.append(_from_pairs("16 straddling HLIT", pairs, 259, True))
+    # 17: symbols 258, 259 and distance symbol 0 are zero; 18: symbols 258 .. 285 and distance symbols 0 .. 3
+    res.append(_from_pairs("17 straddling HLIT", lit258 + [(17, 0)] + _DIST4, 260, True))
+    res.append(_from_pairs("18 straddling HLIT", lit258 + [(18, 21)] + _DIST4, 286, True))
+    # a repeat that ends exactly at HLIT + HDIST, and one past it
+    ends = {16: lit258 + [(4, 0), (16, 3), (16, 3)], 17: lit258 + _DIST4, 18: lit258 + _DIST4}
+    for sym, (exact, size) in {16: (0, 16), 17: (0, 7), 18: (0, 15)}.items():
+        res.append(_from_pairs("%d ending exactly at HLIT + HDIST" % sym, ends[sym] + [(sym, exact)], 258, True))
+        res.append(_from_pairs("%d ending one past HLIT + HDIST" % sym, ends[sym] + [(sym, exact + 1)], 258, code=E_OVERRUN, hdist_field=size - 1))
+        res.append(_from_pairs("%d ending far past HLIT + HDIST" % sym, ends[sym] + [(sym, (1 << K._CL_EXTRA[sym]) - 1)], 258, code=E_OVERRUN, hdist_field=size - 1))
+    # (a 16 with no previous length that also overruns cannot be written: no length has been read only at index 0, where
+    # at most 6 of at least 258 lengths are filled.  The nearest: the smallest alphabets, 16 with the largest extra first)
+    res.append(_from_pairs("16 first, largest extra, smallest alphabets", [(16, 3)] + [(4, 0)] * 252, 257, code=E_NO_PREV, hdist_field=0))
+    return res
+
+
+def _size_streams():
+    res = []
+    for hf in (0, 28, 29, 30, 31):          # 257, 285, 286, 287, 288 literal/length lengths x 1, 29, 30, 31, 32 distance lengths:
+        for df in (0, 28, 29, 30, 31):      # the last symbol of each alphabet has a code (286 / 287 and 30 / 31: coded, unused)
+            hlit, hdist = hf + 257, df + 1
+            lit = _hg_lit(hlit, (hlit - 1, 285))
+            dist = [1] if hdist == 1 else _spread([2] * 4, [0, 1, 2, hdist - 1], hdist)
+            res.append(_hdr("HLIT field %d, HDIST field %d" % (hf, df), True if hlit <= 286 and hdist <= 30 else "ref", lit_lens=lit, dist_lens=dist,
+                            cl_syms=K.cl_rle(lit + dist)))
+    # symbols 286 / 287 and distances 30 / 31 USED: under a short code (first-level entry) and under one longer than the index
+    chain_l, chain_d = list(range(1, 10)) + [10, 10], list(range(1, 9)) + [9, 9]
+    for bad in (286, 287):
+        for long_ in (False, True):
+            lit = _spread(chain_l, [97, 98, 99, 256, 257, 100, 101, 102, 103, 104, bad], 288) if long_ else _hg_lit(288, (bad, 257))
+            res.append(_hdr("symbol %d used, %s code" % (bad, "10-bit" if long_ else "4-bit"), code=E_INVALID, lit_lens=lit, dist_lens=_HG_DIST,
+                            body=lambda w, bad=bad: (w.literal(97), w.literal(98), w.lit_sym(bad), w.bits(0, 20))))
+    for bad in (30, 31):
+        for long_ in (False, True):
+            dist = _spread(chain_d, [0, 1, 2, 3, 4, 5, 6, 7, 8, bad], 32) if long_ else _spread([2] * 4, [0, 1, 2, bad], 32)
+            res.append(_hdr("distance %d used, %s code" % (bad, "9-bit" if long_ else "2-bit"), code=E_INVALID, lit_lens=_hg_lit(), dist_lens=dist,
+                            body=lambda w, bad=bad: (w.literal(97), w.literal(98), w.match(3, 1), w.lit_sym(264), w.dist_sym(bad), w.bits(0, 20))))
+    # no end-of-block code: the block cannot end, the input does
+    res.append(_hdr("no end-of-block code", lit_lens=_spread([4] * 16, list(_HG_LITS[:14]) + [257, 285], 286), dist_lens=_HG_DIST))
+    # nothing but the end-of-block code.  (One code alone has a root table of 2^length entries in the reference: 10 bits
+    # fit its node array, 11 and more do not - huffman-tree.lisp:213-217, constants.lisp:4-7 - and the build fails)
+    for L in (1, 10, 11, 15):
+        only = dict(lit_lens=[0] * 256 + [L], dist_lens=[0])
+        res.append(_hdr("only end-of-block, %d bits" % L, L == 1 or (L == 10 and "ref"), code=E_TREE if L > 10 else None, **only))
+        res.append(_hdr("only end-of-block, %d bits, the other pattern" % L, code=E_TREE if L > 10 else E_INVALID,
+                        body=lambda w, L=L: w.bits((1 << L) - 1, L + 9), **only))
+    return res
+
+
+def _dist_streams():
+    res = []
+    lit = _hg_lit()
+    res.append(_hdr("no distance code, literals only", True, lit_lens=_hg_lit(257, ()), dist_lens=[0]))
+
+    def stale(w):   # a block that defines a distance code, then one without any that has a match
+        w.codes(lit_lens=lit, dist_lens=_HG_DIST)
+        _use_all(w, 30, 5, final=False)
+        w.codes(lit_lens=lit, dist_lens=[0])
+        w.begin_block(True)
+        w.literal(97)
+        w.lit_sym(257)
+        w.bits(0x1234, 16)
+    res.append(_Hdr("no distance code, a match, after a block that had one", stale, stale=True))
+    one = dict(lit_lens=lit, dist_lens=[1])
+    res.append(_hdr("one 1-bit distance code, its pattern", True, body=lambda w: (w.literal(97), w.match(3, 1), w.match(258, 1), w.end_block()), **one))
+    res.append(_hdr("one 1-bit distance code, the other pattern", code=E_INVALID,
+                    body=lambda w: (w.literal(97), w.match(3, 1), w.lit_sym(257), w.bits(0xFFFFF, 20)), **one))
+    for L in (10, 11, 15):   # (the reference's root table again: a single code of 11 bits and more fails the build)
+        res.append(_hdr("one %d-bit distance code, its pattern" % L, L == 10 and "ref", code=E_TREE if L > 10 else None,
+                        body=lambda w: (w.literal(97), w.match(3, 1), w.match(258, 1), w.end_block()), lit_lens=lit, dist_lens=[L]))
+    res.append(_hdr("distance code over-subscribed", code=E_OVERSUB, lit_lens=lit, dist_lens=[1, 1, 1]))
+    res.append(_hdr("distance code incomplete", code=E_INCOMPLETE, lit_lens=lit, dist_lens=[2, 2, 2]))
+    short = _hg_lit(n=15)
+    res.append(_hdr("literal code incomplete and distance code over-subscribed", code=E_INCOMPLETE, lit_lens=short, dist_lens=[1, 1, 1]))
+    res.append(_hdr("literal code over-subscribed and distance code incomplete", code=E_OVERSUB, lit_lens=_hg_lit(n=17), dist_lens=[2, 2, 2]))
+    return res
+
+
+def _longest_header(rle):
+    """288 + 32 code lengths, each sent as one 7-bit symbol (2 240 bits of them: several window refills in the gang
+    leader's fast pass), or the same lengths run-length coded: 224 8-bit and 64 9-bit literal/length codes (286 and 287
+    among them, unused), 32 5-bit distance codes"""
+    lit, dist = [8] * 224 + [9] * 64, [5] * 32
+    if rle:
+        pairs = K.cl_rle(lit + dist)
+        return _hdr("longest header, run-length coded", "ref", lit_lens=lit, dist_lens=dist, cl_syms=pairs, cl_lens=_cl_code(pairs), n_tokens=400)
+    cl = _spread([1, 2, 3, 4, 5, 7, 7, 7, 7], [0, 1, 2, 3, 4, 5, 8, 9, 7], 19)
+    return _hdr("longest header", "ref", lit_lens=lit, dist_lens=dist, cl_lens=cl, n_tokens=400)
+
+
+@functools.lru_cache(None)
+def header_grammar_streams():
+    """-> tuple of _Hdr: every class of case_header_grammar"""
+    res = _hclen_streams() + _cl_shape_streams() + _repeat_streams() + _size_streams() + _dist_streams()
+    res += [_longest_header(False), _longest_header(True)]
+    assert len({h.name for h in res}) == len(res)
+    return tuple(res)
+
+
+def _zlib_header(w):
+    """one of zlib's own headers (a final dynamic block of text), copied bit by bit so that its span is known"""
+    c = zlib.compressobj(9, zlib.DEFLATED, -15)
+    p = K.enwik_like(700, 0x3BA1)
+    z = c.compress(p) + c.flush()
+    assert z[0] & 7 == 5, "zlib did not choose one final dynamic block"
+    for b in z:
+        w.bits(b, 8)
+    w.out += p
+
+
+def damage_bases():
+    """the six headers that are cut and damaged: (name, build)"""
+    by = {h.name: h for h in header_grammar_streams()}
+    edge = code_table_streams()["distance pool of 64: exactly full"]
+    return [by["longest header"], by["18 ending exactly at HLIT + HDIST"], by["one code-length code of 1 bits: zeros by 18"],
+            _Hdr("zlib's own header", _zlib_header), by["HLIT field 31, HDIST field 0"],
+            _Hdr("pool-edge header", lambda w: _table_block(w, *edge, n_tokens=60))]
+
+
+def _prefix_extent(prefix):
+    """(bits, octets of output) of a prefix of _prefixed"""
+    return (0, 0) if prefix is None else (42 * 8, 37) if prefix == "stored" else (10 + 9 * prefix, prefix)
+
+
+def _header_span(s, spans, prefix):
+    """(first bit, bit after) of the first dynamic header of a stream: the writer's span, or - zlib's stream, copied
+    behind the prefix - from the prefix's end to where the oracle, fed octet by octet, first produces output beyond
+    the prefix's (an upper bound within an octet or two: good enough for a sweep)"""
+    if spans:
+        return spans[0]
+    first, n_out = _prefix_extent(prefix)
+    for cut in range(first >> 3, len(s)):
+        if oracle_oneshot(s, "deflate", 4096, end=cut)["offset"] > n_out:
+            return first, cut * 8
+    return first, len(s) * 8
+
+
+def case_header_grammar(eng, stride=509, cut_step=64, prefixes=1):
+    """Dynamic-block headers class by class (header_grammar_streams): every HCLEN; code-length codes of two 1-bit codes, of
+    the full depth, of one code (with and without the unassigned pattern), over-subscribed, incomplete, all zero; the
+    repeat symbols at their limits, first, after each other, across the HLIT boundary, ending at and past the last
+    length; the alphabet sizes the RFC excludes (HLIT fields 30 / 31, HDIST fields 30 / 31) and the symbols they add,
+    coded, unused and used; no end-of-block code and nothing else; distance alphabets that are empty, single, too full,
+    not full, and the precedence of the literal code's error; the longest header there is.  Each stream alone and
+    behind `prefixes` of the nine non-final blocks of _prefixed (in turn; the card: all nine), on every route.
+    Then six headers, each as its item's first block and behind one of the prefixes, cut at every `cut_step`-th octet up
+    to two past their end (and at each of the last four) and with every `stride`-th of their bits flipped (the card:
+    every octet, every bit)."""
+    with k1_routes(eng) as routes:
+        turn = 0
+        for h in header_grammar_streams():
+            for k in range(1 + prefixes):
+                prefix = None if k == 0 else _PREFIXES[1 + (turn + k) % 9]
+                s, p, spans = _prefixed(h.build, prefix)
+                what = "%s, behind %s" % (h.name, prefix)
+                w = _k1_run(routes, s, len(p) + 300, what, plain=p if h.valid else None, stale=h.stale)
+                if h.code is not None:
+                    assert w["flag"] == "error" and w["code"] == h.code, (what, w["flag"], w["code"], h.code)
+            turn += prefixes
+        for h in damage_bases():
+            # as its item's first block (K1h parses it where there is one) and behind one of the prefixes, in turn (the
+            # gang leader does): the sweep starts at the header's first octet, the prefix stays whole
+            for prefix in (None, _PREFIXES[1 + turn % 9]):
+                s, p, spans = _prefixed(h.build, prefix)
+                first, end = _header_span(s, spans, prefix)
+                cap = len(p) + 300
+                last = min(len(s), (end + 7) // 8 + 2)
+                for cut in sorted(set(range((first >> 3) + turn % cut_step, last + 1, cut_step)) | set(range(last - 3, last + 1))):
+                    _k1_run(routes, s, cap, "%s behind %s, cut at %d" % (h.name, prefix, cut), end=cut, stale=True)
+                for bit in range(first + turn % stride, end, stride):
+                    bad = bytearray(s)
+                    bad[bit >> 3] ^= 1 << (bit & 7)
+                    _k1_run(routes, bytes(bad), cap, "%s behind %s, bit %d flipped" % (h.name, prefix, bit), stale=True)
+                turn += 1
+
+
+# ---- code tables
+def kg_pool_need(lens, tb):
+    """kg_build's second-level sizing: a prefix of tb bits that carries codes longer than tb gets 2^(longest - tb)
+    entries -> their sum"""
+    longest = {}
+    for l, c in zip(lens, K.canonical_codes(lens)):
+        if l > tb:
+            longest[c >> (l - tb)] = max(longest.get(c >> (l - tb), 0), l)
+    return sum(1 << (l - tb) for l in longest.values())
+
+
+@functools.lru_cache(None)
+def reachable_needs(tb, max_syms, maxlen=15):
+    """{second-level need: sorted code lengths} over the complete codes of at most max_syms symbols, by search.  In a
+    canonical code the codes longer than tb bits fill whole tb-bit prefixes in order of length, so a prefix is PURE (2^d
+    codes of tb + d bits: 2^d entries for 2^d symbols) or MIXED (depths a .. b below it: 2^b entries for no fewer than
+    2^a + b - a symbols - 2^a - 1 codes of depth a and a chain a + 1, .. b - 1, b, b), and depths never fall from one
+    prefix to the next.  The search walks the chains of mixed prefixes and fills up with pure ones; the codes of tb bits
+    and less are the binary digits of the code space that is left (the fewest symbols that cover it).  Every canonical
+    code has this shape and only the fewest symbols per shape matter, so the walk is exhaustive up to how the pure
+    prefixes split a given need among depths, which changes the count of short codes alone: two splits are tried (all at
+    the least depth, greedy from the greatest).  tests/test_abi_and_host.py checks the result against brute force at a
+    small index width."""
+    D = maxlen - tb
+
+    def chains(floor):
+        yield ()
+        for a in range(floor, D):
+            for b in range(a + 1, D + 1):
+                for rest in chains(b):
+                    yield ((a, b),) + rest
+    best = {}
+    for ch in chains(1):
+        m_need, m_syms = sum(1 << b for a, b in ch), sum((1 << a) + b - a for a, b in ch)
+        allowed = [d for d in range(1, D + 1) if not any(a < d < b for a, b in ch)]
+        for pure in range(0, max_syms - m_syms + 1, 1 << allowed[0]):
+            for order in (allowed, allowed[::-1]):
+                counts, left = {}, pure
+                for d in order if order[0] > order[-1] else order[:1]:
+                    counts[d], left = left >> d, left & ((1 << d) - 1)
+                P = len(ch) + sum(counts.values())
+                if left or not 0 < P <= 1 << tb:
+                    continue
+                lens = [tb - j for j in range(tb + 1) if ((1 << tb) - P) >> j & 1]
+                for a, b in ch:
+                    lens += [tb + a] * ((1 << a) - 1) + [tb + k for k in range(a + 1, b + 1)] + [tb + b]
+                for d, n in counts.items():
+                    lens += [tb + d] * (n << d)
+                need = m_need + pure
+                if 2 <= len(lens) <= max_syms and (need not in best or len(lens) < len(best[need])):
+                    best[need] = sorted(lens)
+    return best
+
+
+def pool_edges(tb, pool, max_syms):
+    """-> {"one step under": lengths, "exactly full": lengths, "one step over": lengths} around a pool of `pool` entries
+    (a step: to the nearest need that a complete code of at most max_syms symbols can have)"""
+    r = reachable_needs(tb, max_syms)
+    res = {"one step under": r[max(t for t in r if t < pool)], "exactly full": r[pool], "one step over": r[min(t for t in r if t > pool)]}
+    for ls in res.values():
+        assert K.kraft(ls) == 1 << 15
+    assert kg_pool_need(res["one step under"], tb) < pool == kg_pool_need(res["exactly full"], tb) < kg_pool_need(res["one step over"], tb)
+    return res
+
+
+_CT_LIT_SYMS = [256, 285, 257, 258, 270, 284] + list(range(32, 256)) + list(range(32)) + [c for c in range(259, 284) if c != 270] + [286, 287]
+
+
+def _ct_lit(lengths, seed):
+    """`lengths` on the literal/length symbols: end-of-block, six length symbols and literals first (all 286 when there
+    are that many), which length goes to which symbol shuffled"""
+    ls = list(lengths)
+    random.Random(seed).shuffle(ls)
+    return _spread(ls, _CT_LIT_SYMS, 286 if len(ls) <= 286 else 288)
+
+
+def _ct_dist(lengths, seed):
+    ls = list(lengths)
+    assert len(ls) <= 30
+    random.Random(seed).shuffle(ls)
+    return ls
+
+
+def _table_block(w, lit, dist, n_tokens=2000):
+    w.codes(lit_lens=lit, dist_lens=dist, cl_syms=K.cl_rle(list(lit) + list(dist)))
+    _use_all(w, n_tokens, len(lit) * 31 + len(dist))
+
+
+@functools.lru_cache(None)
+def code_table_report():
+    """the largest second-level need of a complete literal/length code of 286 and of 288 symbols (zlib's ENOUGH: 340
+    for 286): under the pool of 352 either way, so kg_build's overflow arm cannot be reached for the literal/length
+    code of gangs other than 32"""
+    return {n: max(reachable_needs(KG_TBL, n)) for n in (286, 288)}
+
+
+@functools.lru_cache(None)
+def code_table_streams():
+    """-> {name: (literal/length lengths, distance lengths)}"""
+    flat_l, flat_d = K.match_codes()                    # 9 / 5 / 8 bits and 4 / 5 bits: nothing longer than the index
+    res = {}
+    for pool in (KG_POOLS["dist32"], KG_POOLS["dist"]):
+        for k, ls in pool_edges(KG_TBD, pool, 30).items():
+            res["distance pool of %d: %s" % (pool, k)] = (flat_l, _ct_dist(ls, pool))
+    for k, ls in pool_edges(KG_TBL, KG_POOLS["lit32"], 286).items():
+        res["literal pool of %d: %s" % (KG_POOLS["lit32"], k)] = (_ct_lit(ls, 288), flat_d)
+    rep = code_table_report()
+    assert rep[286] == 340 and rep[286] <= rep[288] < KG_POOLS["lit"], rep    # (340: zlib's ENOUGH for 286 symbols, 9 bits, 15)
+    for n in (286, 288):   # the fullest the pool of 352 can get (288: the two symbols no stream can use are coded)
+        res["literal pool of %d: the most %d symbols need (%d)" % (KG_POOLS["lit"], n, rep[n])] = (_ct_lit(reachable_needs(KG_TBL, n)[rep[n]], n), flat_d)
+    # long codes of exactly index + 1 bits: second-level tables of two entries
+    res["codes of at most 10 and 9 bits"] = (_ct_lit([8] * 240 + [9] * 18 + [10] * 28, 1), _ct_dist(list(range(1, 8)) + [8, 9, 9], 2))
+    # one long prefix with every length under it: the 10-bit code fills 32 entries, the 11-bit one 16 ...
+    res["one long prefix, mixed lengths"] = (_ct_lit(list(range(1, 9)) + [9] + list(range(10, 16)) + [15], 3),
+                                             _ct_dist(list(range(1, 8)) + [8] + list(range(9, 16)) + [15], 4))
+    res["flat codes"] = (flat_l, flat_d)
+    # all 286 symbols, as many of them 15 bits long as Kraft allows
+    n15 = max(n for n in range(2, 286, 2) if n + bin((1 << 15) - n).count("1") <= 286)
+    rest = (1 << 15) - n15
+    skew = [15 - j for j in range(16) if rest >> j & 1]
+    skew += [15] * n15
+    while len(skew) < 286:     # (split the shortest code until every symbol has one)
+        skew.sort()
+        skew[0:1] = [skew[0] + 1] * 2
+    assert K.kraft(skew) == 1 << 15 and len(skew) == 286
+    res["286 symbols, deepest skew"] = (_ct_lit(skew, 5), _ct_dist([4] * 2 + [5] * 28, 6))
+    return res
+
+
+def case_code_tables(eng, n_tokens=600):
+    """kg_build's two-level tables at the edges of its pools (code_table_streams: second-level need one step under, exactly
+    at and one step over the distance pools of 64 and 128 and the literal pool of 288 - over: every long code takes the
+    exact step; the most a literal code can need against the pool of 352), long codes of index + 1 bits only, one long
+    prefix with every length under it (the replicated fill), flat codes, all 286 symbols at the deepest skew.  Every
+    stream uses every coded symbol and decodes `n_tokens` tokens or more (the card: 2 000), alone and behind a non-final
+    block, on every route, and in the default flavour through gangs of 32 as well: the pools of 288 and 64 are theirs."""
+    with k1_routes(eng, gang32=True) as routes:
+        for turn, (name, (lit, dist)) in enumerate(code_table_streams().items()):
+            for prefix in (None, _PREFIXES[1 + turn % 9]):
+                s, p, _ = _prefixed(lambda w: _table_block(w, lit, dist, n_tokens), prefix)
+                _k1_run(routes, s, len(p), "%s, behind %s" % (name, prefix), plain=p)
+                _k1_run(routes, s, len(p), "%s, behind %s, cut" % (name, prefix), end=len(s) * 2 // 3)
+
+
+# ---- tokens
+def _split_to(lens, n):
+    """split the shortest code of a complete code until it has n symbols"""
+    lens = sorted(lens)
+    while len(lens) < n:
+        lens[0:1] = [lens[0] + 1] * 2
+        lens.sort()
+    return lens
+
+
+@functools.lru_cache(None)
+def token_extreme_stream():
+    """32 KiB of aperiodic octets in a stored block, then one dynamic block: 'a' 2 bits, 'b' and 'c' 3, end-of-block and
+    27 length symbols 6, 'd' .. 'm' 5 .. 14, the length symbols 281 and 284 15; distance symbols 28 and 29 15 bits, the
+    others 4 to 14.
+    -> (stream, plain, [(first bit, bit after, output offset) of the widest tokens: 15 + 5 + 15 + 13 bits])"""
+    lit = [0] * 286
+    lit[97], lit[98], lit[99] = 2, 3, 3
+    for c in [256] + [c for c in range(257, 286) if c not in (281, 284)]:
+        lit[c] = 6
+    for k, c in enumerate(range(100, 110)):
+        lit[c] = 5 + k
+    lit[281] = lit[284] = 15
+    dl = _split_to(list(range(1, 15)) + [15, 15], 30)
+    dist = dl[14:28] + dl[:14] + [15, 15]     # (symbols 28 and 29 take the two 15-bit codes)
+    assert K.kraft(lit) == K.kraft(dist) == 1 << 15 and dist[28] == dist[29] == 15
+    w = K.DynamicBlockWriter(lit, dist, cl_syms=K.cl_rle(lit + dist))
+    w.stored(K.xorshift64star_bytes(32768, 0x3BB0))
+    w.begin_block(True)
+    for c in range(97, 110):
+        w.literal(c)
+    for ls in range(257, 286):        # every length symbol at its least and greatest extra bits, the distances in turn
+        top = (1 << K._LEN_EXTRA[ls - 257]) - 1
+        for lx in sorted({0, top}):
+            w.match_syms(ls, lx, (ls * 7 + lx) % 30, 0)
+            w.literal(97 + ls % 3)
+    w.match_syms(284, 31, 0, 0)       # 227 + 31: the other way to write 258
+    for d in range(30):               # every distance symbol at its least and greatest extra bits
+        top = (1 << K._DIST_EXTRA[d]) - 1
+        for dx in sorted({0, top}):
+            w.match_syms(257 + (d * 5 + dx) % 29, 0, d, dx)
+            w.literal(98)
+    wide = []
+    for pos in range(32):             # the widest token from every bit of a 32-bit word: steered by 3- and 2-bit literals
+        while w.bitpos() % 32 != pos:
+            w.literal(97 if (pos - w.bitpos()) % 32 == 2 else 98 + (pos & 1))
+        wide.append((w.bitpos(), w.bitpos() + 48, len(w.out)))
+        w.match_syms(284, 31 - (pos & 1), 29, 8191 - (pos >> 1 & 1))
+        w.literal(100 + pos % 10)
+    w.end_block()
+    s, p = w.finish()
+    return s, p, tuple(wide)
+
+
+def case_token_extremes(eng, every=16):
+    """Behind 32 KiB of stored history, a dynamic block with every length symbol and every distance symbol at its least
+    and greatest extra bits, symbol 284 with extra 31, and the widest token there is - 15 + 5 + 15 + 13 bits - starting
+    at each of the 32 bit positions of a word; then that token cut at every octet inside it and a buffer that ends
+    inside it, for every `every`-th position (the card: each)."""
+    s, p, wide = token_extreme_stream()
+    d = zlib.decompressobj(-15)
+    assert d.decompress(s) == p and d.eof
+    with k1_routes(eng) as routes:
+        _k1_run(routes, s, len(p), "token extremes", plain=p)
+        for k in range(0, 32, every):
+            b0, b1, off = wide[(k + every // 2) % 32 if every > 1 else k]
+            for cut in range(b0 >> 3, (b1 + 7 >> 3) + 1):
+                w = _k1_run(routes, s, len(p), "widest token at bit %d, cut at octet %d" % (b0 % 32, cut), end=cut)
+                assert w["flag"] == "underrun", (cut, w["flag"])
+            for cap in (off, off + 1, off + 100, off + 257):
+                w = _k1_run(routes, s, cap, "widest token at bit %d, buffer of %d" % (b0 % 32, cap))
+                assert w["flag"] == "overflow", (cap, w["flag"])
+
+
 K2_CASES = ["case_match_grid", "case_match_readiness", "case_ring_geometry", "case_symbolic_sources", "case_stored_run_neighbours"]
 
 
@@ -2022,14 +2726,16 @@ ALL_CASES = [case_known_answer_vectors, case_test_deflated, case_reference_chunk
              case_configs_1_3_5, case_overflow_and_underrun, case_errors, case_false_markers, case_device_buffers,
              case_checksum_kernels, case_deep_codes, case_chunked_resume, case_gzip_members,
              case_long_stored_runs, case_pointer_contexts, case_stream_contexts, case_container_headers, case_gzip_metadata, case_scratch_bounds, case_token_density, case_fuzz,
-             case_match_grid, case_match_readiness, case_ring_geometry, case_symbolic_sources, case_stored_run_neighbours]
+             case_match_grid, case_match_readiness, case_ring_geometry, case_symbolic_sources, case_stored_run_neighbours,
+             case_header_grammar, case_code_tables, case_token_extremes]
 # what each engine flavour of the test modules runs.  "auto" runs everything; the others run the cases that can
 # tell them apart (the CPU suite has to stay within minutes: a case costs seconds on the lane emulator)
 FLAVOUR_CASES = {
     # K0b on every stream, however small: candidates, chains through false ones, symbolic history everywhere
     "findalways": ["case_known_answer_vectors", "case_containers_and_levels", "case_noflush_streams",
                    "case_close_block_starts", "case_fixed_block_chains", "case_overflow_and_underrun", "case_false_markers", "case_errors", "case_fuzz",
-                   "case_match_grid", "case_match_readiness", "case_symbolic_sources"],
+                   "case_match_grid", "case_match_readiness", "case_symbolic_sources",
+                   "case_header_grammar", "case_code_tables", "case_token_extremes"],   # (K0b's validator reads the same grammar)
     # chain walk + layout on the host even where the device could (K3)
     "hostlayout": ["case_known_answer_vectors", "case_flush_streams", "case_configs_1_3_5",
                    "case_false_markers", "case_device_buffers", "case_errors", "case_fuzz", "case_match_grid"],
@@ -2043,4 +2749,5 @@ FLAVOUR_CASES = {
 # the cases whose behaviour depends on the K1 flavour (forced-flavour runs skip the rest: checksums, device
 # buffers and the replay protocol go through the same engine calls whatever decodes the Huffman codes)
 K1_CASES = [case_known_answer_vectors, case_test_deflated, case_containers_and_levels, case_fixed_block_chains,
-            case_overflow_and_underrun, case_errors, case_deep_codes, case_fuzz]
+            case_overflow_and_underrun, case_errors, case_deep_codes, case_fuzz,
+            case_header_grammar, case_code_tables, case_token_extremes]

@@ -336,6 +336,192 @@ class DynamicHuffmanWriter(BitWriter):
         self.sym(256)
 
 
+CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)   # RFC 1951 §3.2.7
+CL_FLAT = tuple([4] * 13 + [5] * 6)   # DynamicHuffmanWriter's code-length code: complete, every symbol coded
+
+
+def cl_plain(lens):
+    """the (code-length symbol, extra) pairs that send `lens` one symbol per length"""
+    return [(l, 0) for l in lens]
+
+
+def cl_rle(lens):
+    """... run-length coded, greedily: zeros as 18 (11-138) and 17 (3-10), a repeated length as itself and 16 (3-6)"""
+    out, i, n = [], 0, len(lens)
+    while i < n:
+        v, j = lens[i], i
+        while j < n and lens[j] == v:
+            j += 1
+        run = j - i
+        if v == 0:
+            while run >= 11:
+                k = min(run, 138)
+                out.append((18, k - 11))
+                run -= k
+            if run >= 3:
+                out.append((17, run - 3))
+                run = 0
+        else:
+            out.append((v, 0))
+            run -= 1
+            while run >= 3:
+                k = min(run, 6)
+                out.append((16, k - 3))
+                run -= k
+        out += [(v, 0)] * run
+        i = j
+    return out
+
+
+def cl_expand(pairs):
+    """the lengths a decoder gets from (symbol, extra) pairs (None where RFC 1951 gives them no meaning)"""
+    out = []
+    for s, x in pairs:
+        if s < 16:
+            out.append(s)
+        elif s == 16:
+            if not out:
+                return None
+            out += [out[-1]] * (3 + x)
+        else:
+            out += [0] * ((3 if s == 17 else 11) + x)
+    return out
+
+
+def complete_lengths(n):
+    """a complete code over n symbols (one symbol: a single 1-bit code): 2^k <= n symbols, the first ones k bits"""
+    if n == 1:
+        return [1]
+    k = n.bit_length() - 1
+    short = (2 << k) - n
+    return [k] * short + [k + 1] * (n - short)
+
+
+def kraft(lens):
+    """sum of 2^-l over the coded symbols, in units of 2^-15 (a complete code: 1 << 15)"""
+    return sum(1 << (15 - l) for l in lens if l)
+
+
+_CL_EXTRA = {16: 2, 17: 3, 18: 7}
+
+
+class DynamicBlockWriter(BitWriter):
+    """BTYPE=2 blocks with EVERY header field explicit (DynamicHuffmanWriter keeps its fixed code-length code):
+      lit_lens   257..288 literal/length code lengths, dist_lens 1..32 distance code lengths (the body's codes);
+      cl_lens    the 19 code-length code lengths (default: the flat 4/5-bit code);
+      hclen      how many of them are sent, 4..19 (default: up to the last non-zero one in CL_ORDER);
+      cl_syms    the (code-length symbol, extra) pairs sent (default: cl_plain(lit_lens + dist_lens); cl_rle() gives the
+                 run-length form) - what is sent need not describe lit_lens / dist_lens, nor fit the counts; a pair
+                 ("raw", (value, nbits)) sends those bits as they are;
+      hlit_field / hdist_field   raw 5-bit fields (default: the lists' sizes).
+    codes() sets them again for a later block.  The body is written symbol by symbol: literal / match / end_block track
+    the plaintext in `out`; lit_sym / dist_sym / bits write any symbol, coded or not sensible, and raw bits.  stored()
+    and fixed_literals() write whole blocks of the other types (history, and the bit phase of what follows).
+    `spans` = (first bit, bit after the last) of every dynamic header written, BFINAL and BTYPE included."""
+
+    def __init__(self, lit_lens=None, dist_lens=None, **kw):
+        super().__init__()
+        self.out = bytearray()
+        self.spans = []
+        if lit_lens is not None:
+            self.codes(lit_lens, dist_lens, **kw)
+
+    def codes(self, lit_lens, dist_lens, cl_lens=CL_FLAT, hclen=None, cl_syms=None, hlit_field=None, hdist_field=None):
+        assert 257 <= len(lit_lens) <= 288 and 1 <= len(dist_lens) <= 32 and len(cl_lens) == 19
+        self.lit_lens, self.dist_lens, self.cl_lens = list(lit_lens), list(dist_lens), list(cl_lens)
+        self.lit_codes, self.dist_codes = canonical_codes(self.lit_lens), canonical_codes(self.dist_lens)
+        self.cl_codes = canonical_codes(self.cl_lens)
+        if hclen is None:
+            hclen = max([4] + [k + 1 for k in range(19) if self.cl_lens[CL_ORDER[k]]])
+        assert 4 <= hclen <= 19
+        self.hclen = hclen
+        self.cl_syms = cl_plain(self.lit_lens + self.dist_lens) if cl_syms is None else list(cl_syms)
+        self.hlit_field = len(self.lit_lens) - 257 if hlit_field is None else hlit_field
+        self.hdist_field = len(self.dist_lens) - 1 if hdist_field is None else hdist_field
+
+    def bitpos(self):
+        return len(self.buf) * 8 + self.n
+
+    def begin_block(self, final=False):
+        p0 = self.bitpos()
+        self.bits(1 if final else 0, 1)
+        self.bits(2, 2)
+        self.bits(self.hlit_field, 5)
+        self.bits(self.hdist_field, 5)
+        self.bits(self.hclen - 4, 4)
+        for k in range(self.hclen):
+            self.bits(self.cl_lens[CL_ORDER[k]], 3)
+        for s, x in self.cl_syms:
+            if s == "raw":
+                self.bits(*x)
+            else:
+                self.cl_sym(s, x)
+        self.spans.append((p0, self.bitpos()))
+
+    def cl_sym(self, s, extra=0):
+        assert self.cl_lens[s], s
+        self.code(self.cl_codes[s], self.cl_lens[s])
+        if s >= 16:
+            self.bits(extra, _CL_EXTRA[s])
+
+    def lit_sym(self, s, extra=0, nextra=None):
+        """any literal/length symbol 0..287 that has a code; length symbols take their extra bits"""
+        assert self.lit_lens[s], s
+        self.code(self.lit_codes[s], self.lit_lens[s])
+        if nextra is None:
+            nextra = _LEN_EXTRA[s - 257] if 257 <= s <= 285 else 0
+        if nextra:
+            self.bits(extra, nextra)
+
+    def dist_sym(self, s, extra=0, nextra=None):
+        assert self.dist_lens[s], s
+        self.code(self.dist_codes[s], self.dist_lens[s])
+        if nextra is None:
+            nextra = _DIST_EXTRA[s] if s < 30 else 0
+        if nextra:
+            self.bits(extra, nextra)
+
+    def literal(self, b):
+        self.lit_sym(b)
+        self.out.append(b)
+
+    def match_syms(self, lsym, lextra, dsym, dextra):
+        """a match by its two symbols and their extra bits (symbol 284 with extra 31 is a length of 258 too)"""
+        length, dist = _LEN_BASE[lsym - 257] + lextra, _DIST_BASE[dsym] + dextra
+        assert 257 <= lsym <= 285 and 0 <= lextra < 1 << _LEN_EXTRA[lsym - 257] and length <= 258, (lsym, lextra)
+        assert 1 <= dist <= min(len(self.out), 32768) and dextra < 1 << _DIST_EXTRA[dsym], (dist, len(self.out))
+        self.lit_sym(lsym, lextra)
+        self.dist_sym(dsym, dextra)
+        lz_apply_octets(self.out, length, dist)
+
+    def match(self, length, dist):
+        li = max(i for i in range(29) if _LEN_BASE[i] <= length) if length < 258 else 28
+        di = max(i for i in range(30) if _DIST_BASE[i] <= dist)
+        self.match_syms(257 + li, length - _LEN_BASE[li], di, dist - _DIST_BASE[di])
+
+    def end_block(self):
+        self.lit_sym(256)
+
+    def stored(self, data, final=False):
+        self.bits(1 if final else 0, 3)
+        self.align()
+        self.buf += struct.pack("<HH", len(data), len(data) ^ 0xFFFF) + data
+        self.out += data
+
+    def fixed_literals(self, data, final=False):
+        """a fixed-Huffman block of literals: 10 bits and 8 or 9 per literal (9 from octet 144 on)"""
+        self.bits(1 if final else 0, 1)
+        self.bits(1, 2)
+        for c in data:
+            self.bits(*_FIXED_LIT[c])
+        self.bits(0, 7)
+        self.out += data
+
+    def finish(self):
+        self.align()
+        return self.getvalue(), bytes(self.out)
+
+
 def deep_code_stream(n_tokens=40000, seed=7, dist_overflow=False, blocks=3):
     """Raw deflate stream of dynamic blocks whose codes are as deep as RFC 1951 allows.
     lit/len: 16 symbols coded with lengths 1,2,...,14,15,15 (literals, end-of-block and five length symbols),
