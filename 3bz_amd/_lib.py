@@ -54,6 +54,8 @@ SYMBOLS = [
     "tbz_gzip_header_parse", "tbz_inflate_gzip_members", "tbz_inflate_gzip_members_device",
     "tbz_inflate_to_device", "tbz_assign_streams", "tbz_inflate_batch_multi", "tbz_inflate_batch_multi_device",
     "tbz_inflate_sharded_plan", "tbz_inflate_sharded_verdict", "tbz_inflate_sharded_multi",
+    "tbz_index_build", "tbz_index_build_device", "tbz_index_destroy", "tbz_index_info", "tbz_index_points",
+    "tbz_index_export", "tbz_index_import", "tbz_inflate_ranges", "tbz_inflate_ranges_device",
 ]
 
 
@@ -118,6 +120,17 @@ def load(path=None):
     L.tbz_inflate_sharded_verdict.argtypes = [C.c_int, vp, sz, sz, u64p, C.POINTER(Result), C.POINTER(C.c_uint32), u64p, u64p,
                                               C.POINTER(C.c_uint32), u64p, C.POINTER(C.c_int)]
     L.tbz_inflate_sharded_multi.argtypes = [C.POINTER(vp), sz, C.c_int, vp, sz, vp, sz, C.POINTER(Result), C.POINTER(C.c_int)]
+    szp = C.POINTER(sz)
+    L.tbz_index_build_device.argtypes = [vp, C.c_int, vp, sz, sz, C.POINTER(vp), C.POINTER(Result)]
+    L.tbz_index_build.argtypes = [vp, C.c_int, vp, sz, sz, C.POINTER(vp), C.POINTER(Result)]
+    L.tbz_index_destroy.argtypes = [vp]
+    L.tbz_index_destroy.restype = None
+    L.tbz_index_info.argtypes = [vp, C.POINTER(C.c_int), szp, szp, szp, szp]
+    L.tbz_index_points.argtypes = [vp, sz, u64p, u64p]
+    L.tbz_index_export.argtypes = [vp, vp, sz, szp]
+    L.tbz_index_import.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    L.tbz_inflate_ranges_device.argtypes = [vp, vp, vp, sz, sz, u64p, u64p, vp, u64p, C.POINTER(Result)]
+    L.tbz_inflate_ranges.argtypes = [vp, vp, vp, sz, sz, u64p, u64p, C.POINTER(vp), C.POINTER(Result)]
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the ABI is incomplete
     return L

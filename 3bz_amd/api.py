@@ -13,6 +13,7 @@ behaviour — so the parity tests read like the reference's REPL tests:
 Everything runs on the MI355X through lib3bz_amd.so; nothing here decodes on the CPU.
 """
 import ctypes as C
+import weakref
 
 from . import _lib
 
@@ -58,9 +59,12 @@ class Engine:
             raise EngineError(r, self.lib.tbz_strerror(r).decode())
         self._ctx = p
         self.device = device
+        self._indices = weakref.WeakSet()   # live Index objects: a tbz_index is released before its context (tbz_amd.h)
 
     def close(self):
         if getattr(self, "_ctx", None):
+            for ix in list(getattr(self, "_indices", ())):
+                ix.close()
             self.lib.tbz_ctx_destroy(self._ctx)
             self._ctx = None
 
@@ -275,6 +279,50 @@ class Engine:
         self._check(self.lib.tbz_session_stats(sess, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    # ---- seek index and byte-range decode (random access into one stream)
+    def index_build(self, data, fmt, spacing=0, start=0, end=None):
+        """tbz_index_build over host octets: (Index or None, result) — None when the stream does not decode to finished
+        (result.status says why)"""
+        end = len(data) if end is None else end
+        res, p = _lib.Result(), C.c_void_p()
+        base = _addr(data)
+        self._check(self.lib.tbz_index_build(self._ctx, fmt, (base or 0) + start if base else None, end - start, spacing,
+                                             C.byref(p), C.byref(res)))
+        return (Index(self, p) if p.value else None), res
+
+    def index_build_device(self, d_in, in_len, fmt, spacing=0):
+        """the same with the stream in HBM (a raw device pointer)"""
+        res, p = _lib.Result(), C.c_void_p()
+        self._check(self.lib.tbz_index_build_device(self._ctx, fmt, d_in, in_len, spacing, C.byref(p), C.byref(res)))
+        return (Index(self, p) if p.value else None), res
+
+    def index_import(self, blob):
+        """tbz_index_import: an Index from Index.export()'s octets (EngineError TBZ_E_ARG for a blob that is not sound)"""
+        p = C.c_void_p()
+        blob = bytes(blob)
+        self._check(self.lib.tbz_index_import(self._ctx, _addr(blob) if blob else None, len(blob), C.byref(p)))
+        return Index(self, p)
+
+    def inflate_ranges(self, index, data, offs, lens, outs, start=0, end=None):
+        """tbz_inflate_ranges: octets [offs[i], offs[i] + lens[i]) of the stream's OUTPUT into outs[i] (host buffers)"""
+        end = len(data) if end is None else end
+        n = len(offs)
+        a = self.u64_array
+        res = (_lib.Result * max(1, n))()
+        base = _addr(data)
+        self._check(self.lib.tbz_inflate_ranges(self._ctx, index._ix, (base or 0) + start if base else None, end - start, n,
+                                                a(offs), a(lens), (C.c_void_p * max(1, n))(*[_addr(o) for o in outs]), res))
+        return list(res)[:n]
+
+    def inflate_ranges_device(self, index, d_in, in_len, offs, lens, d_out, out_offs):
+        """tbz_inflate_ranges_device: the stream and the destination in HBM; range i goes to d_out + out_offs[i]"""
+        n = len(offs)
+        a = self.u64_array
+        res = (_lib.Result * max(1, n))()
+        self._check(self.lib.tbz_inflate_ranges_device(self._ctx, index._ix, d_in, in_len, n, a(offs), a(lens), d_out,
+                                                       a(out_offs), res))
+        return list(res)[:n]
+
     def trim(self):
         """release the context's device scratch (it only grows otherwise)"""
         self._check(self.lib.tbz_ctx_trim(self._ctx))
@@ -286,6 +334,52 @@ class Engine:
 
     def strerror(self, code):
         return self.lib.tbz_strerror(code).decode()
+
+
+class Index:
+    """a tbz_index: the proven block starts of one stream, their windows and interval checksums, on one engine"""
+
+    def __init__(self, engine, ptr):
+        self._eng, self._ix = engine, ptr
+        engine._indices.add(self)
+
+    def close(self):
+        """release the index (Engine.close does it for every index still open on it: the context goes last)"""
+        if getattr(self, "_ix", None) and getattr(self._eng, "_ctx", None):
+            self._eng.lib.tbz_index_destroy(self._ix)
+        self._ix = None
+        self._eng._indices.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """dict: format, in_len, out_total, n_points, max_interval"""
+        f = C.c_int()
+        v = [C.c_size_t() for _ in range(4)]
+        self._eng._check(self._eng.lib.tbz_index_info(self._ix, C.byref(f), *[C.byref(x) for x in v]))
+        return {"format": f.value, "in_len": v[0].value, "out_total": v[1].value, "n_points": v[2].value,
+                "max_interval": v[3].value}
+
+    def points(self):
+        """list of (in_bit, out_off)"""
+        n = self.info()["n_points"]
+        a, b = (C.c_uint64 * n)(), (C.c_uint64 * n)()
+        k = self._eng.lib.tbz_index_points(self._ix, n, a, b)
+        if k < 0:
+            self._eng._check(k)
+        return list(zip(a[:k], b[:k]))
+
+    def export(self):
+        """the index as bytes, for Engine.index_import in another process or on another device"""
+        need = C.c_size_t()
+        self._eng._check(self._eng.lib.tbz_index_export(self._ix, None, 0, C.byref(need)))
+        buf = bytearray(need.value)
+        self._eng._check(self._eng.lib.tbz_index_export(self._ix, _addr(buf), len(buf), C.byref(need)))
+        return bytes(buf)
 
 
 _default = None
@@ -702,3 +796,34 @@ def decompress_gzip_members(compressed, start=0, end=None, engine=None):
             raise ThreeBzError(-20, "incomplete gzip stream")
         members.append(b)
     return members
+
+
+# ------------------------------------------------------------------------------------------------
+# Random access.  The reference's :start / :end select INPUT octets (api.lisp:23-29) and a stream is decoded from its
+# first block; an index (include/tbz_amd.h, tbz_index_*) lets a caller ask for OUTPUT octets instead.
+# ------------------------------------------------------------------------------------------------
+def build_index(compressed, format="zlib", spacing=0, engine=None):
+    """decode the stream once and keep its proven block starts: an Index.  A stream that decompress_vector would not
+    accept raises what decompress_vector raises."""
+    fmt = FORMATS[format] if isinstance(format, str) else format
+    name = format if isinstance(format, str) else {0: "deflate", 1: "zlib", 2: "gzip"}[fmt]
+    eng = engine or default_engine()
+    ix, res = eng.index_build(compressed, fmt, spacing)
+    if res.status < 0:
+        raise ThreeBzError(res.status, eng.strerror(res.status))
+    if ix is None:
+        raise ThreeBzError(-20, "incomplete %s stream" % name)
+    return ix
+
+
+def decompress_ranges(compressed, index, ranges, engine=None):
+    """octets [off, off + len) of the stream's output for every (off, len) of `ranges`: a list of bytearrays (clipped at
+    the end of the stream like read(2)).  A range whose part of the stream is damaged raises ThreeBzError."""
+    eng = engine or index._eng
+    total = index.info()["out_total"]
+    outs = [bytearray(max(0, min(ln, total - off))) for off, ln in ranges]
+    res = eng.inflate_ranges(index, compressed, [r[0] for r in ranges], [r[1] for r in ranges], outs)
+    for r in res:
+        if r.status < 0:
+            raise ThreeBzError(r.status, eng.strerror(r.status))
+    return outs

@@ -27,8 +27,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/tbz_amd.h"
@@ -56,7 +58,8 @@ struct DevBuf {
   X(d_out_stage) X(d_kb_tf) X(d_kb_slots) X(d_kb_counts) X(d_kb_offsets) X(d_kb_cands) X(d_kb_fc) X(d_kb_head) \
   X(d_markers2) X(d_kb_fm2) X(d_mark) X(d_hg) X(d_k6s) X(d_bigs) X(d_recs) X(d_kc_tf) \
   X(d_kc_slots) X(d_kc_ends) X(d_kc_link) X(d_kc_fm2) X(d_markers3) X(d_kb_keep) X(d_kb_kcounts) X(d_gz_cands) \
-  X(d_gz_count) X(d_gz_tmp) X(d_wide_res) X(d_cold) X(d_cold2) X(d_small_rec)
+  X(d_gz_count) X(d_gz_tmp) X(d_wide_res) X(d_cold) X(d_cold2) X(d_small_rec) \
+  X(d_bit_off) X(d_ix_span) X(d_ix_recs)
 
 namespace tbz {
 // A few host threads that copy between a caller's (pageable) buffer and the pinned staging buffers: one thread moves
@@ -588,10 +591,13 @@ static int run_adler_groups(tbz_ctx* ctx, const std::vector<uint32_t>& first_gro
   return read_back(ctx, out.data(), ctx->d_ck_out.p, n * sizeof(uint32_t));
 }
 
-// what a resumable session (tbz_session_*) and the allocate-once entry point ask of the pipeline beyond a plain call;
-// only for calls of ONE stream
+// what a resumable session (tbz_session_*), the allocate-once entry point and the seek index (tbz_index_*,
+// tbz_inflate_ranges*) ask of the pipeline beyond a plain call
 struct CoreOpts {
-  // ---- in
+  // ---- in, per stream (calls of any number of streams; nullptr: start_bit_off / hist_len below for stream 0, 0 for the rest)
+  const uint32_t* start_bit_offs = nullptr;  // stream s's first block header sits at this bit of its first octet
+  const uint64_t* hist_lens = nullptr;       // octets of earlier output directly in front of out_offs[s] in the output buffer
+  // ---- in, calls of ONE stream only
   uint32_t start_bit_off = 0;  // the stream's first block header sits at this bit of its first octet (a continuation:
                                // raw blocks entered at a block boundary, deflate.lisp:518-528 needs no other state)
   uint64_t resume_tok_bit = 0; // != 0: a continuation INSIDE a block — the block's header is parsed at start_bit_off, then the
@@ -600,6 +606,8 @@ struct CoreOpts {
                                // out_off - hist_len ...): matches may reach into them (deflate.lisp:343-352, the window)
   bool prefix_on_error = false;  // a stream that fails is still laid out and decoded up to the failing token
                                  // (tbz_result.out_total = that many octets), as a front-to-back decoder would have
+  bool want_points = false;      // the seek index is being built: the general (host) layout path whatever the chain looks like,
+                                 // the block-start finder whatever the stream's size, and `points` below
   // the output buffer is obtained once the size is known: total octets -> device pointer of a buffer in which the
   // stream's output starts at octet `out_offs[0]` (and that holds total + 64 octets from there)
   std::function<void*(uint64_t total)> alloc;
@@ -613,6 +621,10 @@ struct CoreOpts {
   uint64_t end_bit = 0;        // finished: bit position after the final block (octet-aligned, before any trailer the
                                // engine did not parse because the format was raw deflate)
   int32_t first_error = 0;     // prefix_on_error: the status a plain call would have reported (0 if none)
+  // want_points: every proven segment's (start bit from the stream's first octet, output octets before it), in order.  A
+  // segment that continues a repaired block starts at a block start too.  The first entry is the head item's: it starts
+  // at the container header, not at a block.
+  std::vector<std::pair<uint64_t, uint64_t>> points;
 };
 
 // ---- one small stream in ONE launch (tbz_small_fused, tbz_kernels.hpp): the kernel decides the clean case only —
@@ -866,9 +878,14 @@ struct Call {
   bool size_only;
   CoreOpts* opt;
   // ---- derived from them
-  uint64_t hist_len = 0;
-  uint32_t bit_off = 0;
+  std::vector<uint64_t> hist;     // per stream: CoreOpts::hist_lens (empty: none anywhere)
+  std::vector<uint32_t> bit_off;  // per stream: CoreOpts::start_bit_offs (empty: 0 everywhere)
+  const u32* d_bit_off = nullptr; // ... on the device (call_k0)
+  uint64_t hist_of(size_t s) const { return hist.empty() ? 0 : hist[s]; }
+  uint32_t bit_off_of(size_t s) const { return bit_off.empty() ? 0 : bit_off[s]; }
   uint64_t resume_abs = 0;
+  bool host_layout = false;  // the context's switch, or CoreOpts::want_points
+  int find_mode = 1;         // the context's TBZ_FIND mode, or 2 with CoreOpts::want_points
   // ---- K0 / K0b / K0c: the stream table, the markers (flush points, block-start candidates), the K1 items built from them
   std::vector<StreamPlan> sp;
   uint64_t tiles = 0, in_lo = ~0ull, in_extent = 0, in_total_bits = 0;
@@ -914,10 +931,23 @@ static int call_begin(Call& c, bool* done) {
   if (!ctx || !c.results || (n && (!c.in_offs || !c.in_lens))) return TBZ_E_ARG;
   if (c.format < 0 || c.format > 2) return TBZ_E_ARG;
   if (!c.size_only && n && (!c.out_offs || !c.out_caps)) return TBZ_E_ARG;
-  if (opt && n != 1) return TBZ_E_ARG;
-  c.hist_len = opt ? opt->hist_len : 0;
-  if (c.hist_len && !ctx->sym_hist) return TBZ_E_UNSUPPORTED;  // (TBZ_HIST=off: no way to reach octets of an earlier call)
-  c.bit_off = opt ? opt->start_bit_off : 0;
+  // several streams: only the per-stream re-entry state and alloc; the rest stay one-stream features
+  if (opt && n != 1 &&
+      (n == 0 || opt->start_bit_off || opt->hist_len || opt->resume_tok_bit || opt->prefix_on_error || opt->want_points))
+    return TBZ_E_ARG;
+  c.host_layout = ctx->host_layout || (opt && opt->want_points);
+  c.find_mode = (opt && opt->want_points) ? 2 : ctx->find_mode;
+  if (opt && (opt->hist_lens || opt->hist_len)) {
+    c.hist.assign(n, 0);
+    for (size_t s = 0; s < n; s++) c.hist[s] = opt->hist_lens ? opt->hist_lens[s] : (s == 0 ? opt->hist_len : 0);
+    if (std::all_of(c.hist.begin(), c.hist.end(), [](uint64_t h) { return h == 0; })) c.hist.clear();
+  }
+  if (!c.hist.empty() && !ctx->sym_hist) return TBZ_E_UNSUPPORTED;  // (TBZ_HIST=off: no way to reach octets of an earlier call)
+  if (opt && (opt->start_bit_offs || opt->start_bit_off)) {
+    c.bit_off.assign(n, 0);
+    for (size_t s = 0; s < n; s++) c.bit_off[s] = opt->start_bit_offs ? opt->start_bit_offs[s] : (s == 0 ? opt->start_bit_off : 0);
+    if (std::all_of(c.bit_off.begin(), c.bit_off.end(), [](uint32_t b) { return b == 0; })) c.bit_off.clear();
+  }
   c.resume_abs = (opt && opt->resume_tok_bit && n) ? c.in_offs[0] * 8 + opt->resume_tok_bit : 0;
   TBZ_HIP(hipSetDevice(ctx->device));
   ctx->tim = tbz_timings{};
@@ -993,10 +1023,14 @@ static int call_k0(Call& c) {
     if ((r = ensure(ctx, ctx->d_markers, tiles * (size_t)K0_SLOTS * 8 + 16))) return r;
     if ((r = ensure(ctx, ctx->d_k0_fm, (n + 1) * 4 + 16))) return r;  // [0..1] head, [2..] first_marker, [n+3] fixed-block items, [n+4] stored heads
     if ((r = ensure(ctx, ctx->d_items, (tiles * (size_t)K0_SLOTS + n) * sizeof(Item)))) return r;
+    if (!c.bit_off.empty()) {
+      if ((r = upload(ctx, ctx->d_bit_off, c.bit_off))) return r;
+      c.d_bit_off = (const u32*)ctx->d_bit_off.p;
+    }
     K0Params k0{(const u8*)c.d_in, (const u64*)ctx->d_str_off.p, (const u64*)ctx->d_str_len.p,
                 (const u32*)ctx->d_tile_first.p, (u32)n, (u32)tiles, (u32*)ctx->d_tile_counts.p,
                 (u32*)ctx->d_tile_offsets.p, (u64*)ctx->d_markers.p, (u64*)ctx->d_k0_slots.p,
-                (u32*)ctx->d_k0_fm.p + 2, (u32*)ctx->d_k0_fm.p, (Item*)ctx->d_items.p, (u32)c.format, 0, c.bit_off,
+                (u32*)ctx->d_k0_fm.p + 2, (u32*)ctx->d_k0_fm.p, (Item*)ctx->d_items.p, (u32)c.format, 0, c.d_bit_off,
                 (u32*)ctx->d_k0_fm.p + (n + 3), c.resume_abs ? 1u : 0u};
     const size_t max_items = tiles * (size_t)K0_SLOTS + n;
     TBZ_LAUNCH(tbz_k0_scan_tiles, tiles, ctx->stream, k0);
@@ -1027,7 +1061,7 @@ static int call_k0(Call& c) {
     if ((r = upload(ctx, ctx->d_k0_fm, zero))) return r;
     for (size_t s = 0; s < n; s++) {
       Item it{};
-      it.start_bit = c.sp[s].in_off * 8 + (s == 0 ? c.bit_off : 0);
+      it.start_bit = c.sp[s].in_off * 8 + c.bit_off_of(s);
       it.limit_bit = ~0ull;
       it.end_byte = c.sp[s].in_off + c.sp[s].in_len;
       it.stream = (uint32_t)s;
@@ -1054,7 +1088,7 @@ static int search_tiles(Call& c, uint64_t tile, bool enough, uint64_t min_len, u
     tf[s] = (uint32_t)t;
     const uint64_t items_s = 1 + (c.first_marker[s + 1] - c.first_marker[s]);
     const uint64_t len = c.sp[s].in_len;
-    const bool search = ctx->find_mode == 2 ? len >= 64 : (!enough && len >= min_len && len * 8 / items_s >= min_item_bits);
+    const bool search = c.find_mode == 2 ? len >= 64 : (!enough && len >= min_len && len * 8 / items_s >= min_item_bits);
     if (search) t += ((((uintptr_t)c.d_in + c.in_offs[s]) & 15) + c.in_lens[s] + tile - 1) / tile;
     if (t > 0x7fffffffu) return TBZ_E_ARG;
   }
@@ -1087,7 +1121,7 @@ static int search_setup(Call& c, uint64_t tiles, u32 slots, DevBuf& tf, DevBuf& 
                  (const u32*)tf.p, (u32)n, (u32)tiles, (u64*)cand_slots.p, (u32*)ctx->d_kb_counts.p,
                  (u32*)ctx->d_kb_offsets.p, (u64*)ctx->d_kb_cands.p, (u32*)ctx->d_kb_fc.p, (u32*)ctx->d_kb_head.p,
                  c.d_markers_cur, c.d_first_marker, (u64*)markers.p,
-                 (u32*)fm2.p + 2, (u32*)fm2.p, c.bit_off, slots, 0, nullptr, nullptr,
+                 (u32*)fm2.p + 2, (u32*)fm2.p, c.d_bit_off, slots, 0, nullptr, nullptr,
                  (u64*)ctx->d_kb_keep.p, (u32*)ctx->d_kb_kcounts.p, 0};
   return 0;
 }
@@ -1128,7 +1162,7 @@ static int merge_candidates(Call& c, const K0bParams& kb, DevBuf& markers, DevBu
     k0m.items = (Item*)ctx->d_items.p;
     k0m.format = (u32)c.format;
     k0m.second_pass = 1;
-    k0m.start_bit_off = c.bit_off;
+    k0m.start_bit_off = c.d_bit_off;
     k0m.resume = c.resume_abs ? 1u : 0u;
     TBZ_LAUNCH(tbz_k0_items, ((size_t)c.n_mark + n + 63) / 64, ctx->stream, k0m);
     c.d_markers_cur = (const u64*)markers.p;
@@ -1147,12 +1181,12 @@ static int merge_candidates(Call& c, const K0bParams& kb, DevBuf& markers, DevBu
 // and the items are built again from the merged list.  Nothing downstream tells a candidate from a marker.
 static int call_k0b(Call& c) {
   tbz_ctx* ctx = c.ctx;
-  if (!c.tiles || !ctx->find_mode) return 0;
+  if (!c.tiles || !c.find_mode) return 0;
   constexpr uint64_t FIND_MIN_ITEM_BITS = 8ull * (48u << 10);  // mean compressed octets per item below which it does not pay
   // ... nor when the call already has enough items to fill the chip (a batch of thousands of streams: measured on
   // config 3, 4096 gzip members, splitting them cost more in K2's second plane than it gained in K1)
   // ... nor when every stream begins with a stored block (stored data: nothing to find; config 1)
-  const bool enough = (size_t)c.n_mark + c.n >= (size_t)ctx->tun.find_enough || (c.n_stored_heads >= c.n && ctx->find_mode != 2);
+  const bool enough = (size_t)c.n_mark + c.n >= (size_t)ctx->tun.find_enough || (c.n_stored_heads >= c.n && c.find_mode != 2);
   uint64_t tiles_b = 0;
   int r;
   if ((r = search_tiles(c, K0B_TILE, enough, (uint64_t)ctx->tun.find_min_len, FIND_MIN_ITEM_BITS, ctx->d_kb_tf, &tiles_b))) return r;
@@ -1181,7 +1215,7 @@ static int call_k0b(Call& c) {
 // searched for "end-of-block + BTYPE 1" patterns; each hit's one block is skimmed and the hits that chain are kept.
 static int call_k0c(Call& c) {
   tbz_ctx* ctx = c.ctx;
-  if (!c.tiles || !ctx->find_mode) return 0;
+  if (!c.tiles || !c.find_mode) return 0;
   constexpr uint64_t FIXED_MIN_ITEM_BITS = 8ull * (256u << 10);
   // flush-delimited items that begin with fixed-Huffman blocks (K0 counted them) are chains of such blocks, and a
   // periodic bitstream — what fixed-Huffman territory tends to be — never lets K1's lanes fall into step: block starts
@@ -1465,7 +1499,7 @@ static int launch_k1(Call& c, const Item* d_items, SegResult* d_res, size_t n_it
 static int call_k1(Call& c) {
   tbz_ctx* ctx = c.ctx;
   const size_t n = c.n, n_items = c.n_items;
-  const bool try_simple = !ctx->host_layout && n_items != 0;
+  const bool try_simple = !c.host_layout && n_items != 0;
   const u32 k3_tiles = (u32)((n_items + K3_TILE - 1) / K3_TILE);
   int r;
   if (try_simple) {
@@ -1742,7 +1776,7 @@ static int call_chain_walk(Call& c, const std::vector<SegResult>& res) {
         it.end_byte = c.sp[s].in_off + c.sp[s].in_len;
         it.stream = (uint32_t)s;
         it.flags = ((uint32_t)c.format << ITEM_FMT_SHIFT) | ITEM_FIXUP;
-        if (c.resume_abs && s == 0 && it.start_bit == c.sp[0].in_off * 8 + c.bit_off) it.flags |= ITEM_RESUME;  // (the block the session resumes in)
+        if (c.resume_abs && s == 0 && it.start_bit == c.sp[0].in_off * 8 + c.bit_off_of(0)) it.flags |= ITEM_RESUME;  // (the block the session resumes in)
         fix.push_back(it);
       }
     if (fix.empty()) break;
@@ -1804,7 +1838,7 @@ static int call_distance(Call& c) {
   std::vector<Probe> pv;
   for (size_t s = 0; s < n; s++) {
     uint64_t produced = 0;
-    const uint64_t hist = s == 0 ? c.hist_len : 0;  // (a resumed stream: octets of earlier output that are there to copy from)
+    const uint64_t hist = c.hist_of(s);  // (a resumed stream: octets of earlier output that are there to copy from)
     for (size_t i = 0; i < c.per_stream[s].size(); i++) {
       const SegHost& h = c.per_stream[s][i];
       if (h.deficit && (uint64_t)h.deficit > produced + hist) {
@@ -1835,7 +1869,7 @@ static int call_distance(Call& c) {
     h.seg.n_runs = pr[k].n_runs;
     h.seg.run0 = pr[k].run0;
     const uint64_t at = pr[k].reserved;  // octets into the item; ~0: none found (cannot happen)
-    const uint64_t hist_k = pv[k].s == 0 ? c.hist_len : 0;
+    const uint64_t hist_k = c.hist_of(pv[k].s);
     c.dist_first[pv[k].s] = (at != ~0ull && pv[k].before - hist_k + at > c.sp[pv[k].s].out_cap) ? DIST_AFTER_OVERFLOW : DIST_FIRST;
     if (at != ~0ull) c.dist_at = pv[k].before - hist_k + at;  // octets of the stream before the offending match
   }
@@ -1875,7 +1909,7 @@ static int call_groups(Call& c) {
       R.out_total = R.out_len;
     }
     if (c.size_only) continue;
-    const uint64_t hist = s == 0 ? c.hist_len : 0;
+    const uint64_t hist = c.hist_of(s);
     // groups: consecutive segments that share one LZ77 window in one K2 workgroup.  A segment that needs no history
     // opens a group of its own.  One that does (its matches reach before its first octet, or it continues a
     // repaired block) joins the group before it while that group is small; a group whose segments reach before
@@ -2005,7 +2039,7 @@ static int call_host_k2(Call& c) {
         const StreamPlan& S = c.sp[c.h_gstream[gi]];
         order_h.push_back((uint32_t)gi);
         hgs.push_back(HGroupSpan{c.h_groups[gi].out_abs, std::max(c.h_groups[gi].out_abs, std::min(c.h_groups[gi].out_abs + tot, c.h_groups[gi].out_end)),
-                         S.out_off - (c.h_gstream[gi] == 0 ? c.hist_len : 0), c.h_gstream[gi]});
+                         S.out_off - c.hist_of(c.h_gstream[gi]), c.h_gstream[gi]});
         mark_lo = std::min(mark_lo, S.out_off);
         mark_hi = std::max(mark_hi, c.h_groups[gi].out_end);
       } else if (tot + K2_SLACK <= K2_SMALL_MAX) {
@@ -2081,6 +2115,14 @@ static int call_finish(Call& c) {
   if ((r = record(ctx, 6))) return r;
   TBZ_HIP(hipStreamSynchronize(ctx->stream));
   const bool keep_prefix = opt && opt->prefix_on_error;
+  if (opt && opt->want_points) {
+    opt->points.clear();
+    uint64_t before = 0;
+    for (const SegHost& h : c.per_stream[0]) {
+      opt->points.push_back({h.item.start_bit - S0.in_off * 8, before});
+      before += h.seg.out_bytes;
+    }
+  }
   if (opt) {
     opt->blk_known = S0.blk_known;
     opt->blk_bit = S0.blk_bit > S0.in_off * 8 ? S0.blk_bit - S0.in_off * 8 : 0;
@@ -3868,6 +3910,553 @@ int tbz_memcpy_d2h(tbz_ctx* ctx, void* h_dst, const void* d_src, size_t bytes) {
   TBZ_HIP(hipSetDevice(ctx->device));
   if (bytes) TBZ_HIP(hipMemcpy(h_dst, d_src, bytes, hipMemcpyDeviceToHost));
   return 0;
+}
+
+}  // extern "C"
+
+// ====================================================================================================
+// Seek index and byte-range decode (tbz_index_*, tbz_inflate_ranges*): random access into one stream.
+// The reference decodes front to back only (deflate.lisp:719-722; decompress-vector's :start / :end select input,
+// api.lisp:23-29).  Here the block starts the engine PROVES while it decodes a stream once are kept — bit position,
+// output offset, the 32 KiB window in front, a crc32 per interval — and a range is served by decoding only the
+// intervals that cover it: every span of intervals is one raw-deflate stream of ONE inflate_core call, entered at its
+// point's bit (CoreOpts::start_bit_offs) with the point's window in front of its output (CoreOpts::hist_lens).
+// ====================================================================================================
+struct tbz_index {
+  tbz_ctx* ctx = nullptr;
+  int format = 0;
+  uint64_t in_len = 0, out_total = 0, first_block_bit = 0;
+  uint32_t check = 0;              // the stream's whole-output checksum (adler32 / crc32 by format; 0 for raw deflate)
+  std::vector<uint64_t> in_bit, out_off;
+  std::vector<uint32_t> win_len;   // min(out_off, 32768)
+  std::vector<uint64_t> win_off;   // where the window lies in d_win (16-aligned)
+  std::vector<uint32_t> crc;       // crc32 (init 0) of the output octets [out_off[k], out_off[k + 1]) (the last: to out_total)
+  void* d_win = nullptr;
+  uint64_t win_bytes = 0;
+  uint64_t interval_end(size_t k) const { return k + 1 < out_off.size() ? out_off[k + 1] : out_total; }
+};
+
+namespace tbz {
+constexpr uint32_t IX_MAGIC = 0x585a4254u;  // "TBZX"
+constexpr uint32_t IX_VERSION = 1;
+constexpr size_t IX_HEAD = 56;              // the blob's scalar fields (see tbz_index_export)
+constexpr uint64_t IX_MIN_IN_BITS = 512;    // successive points are at least 64 input octets apart
+constexpr uint64_t IX_WIN = 32768;
+
+static uint32_t ix_crc32(const uint8_t* p, size_t n) {  // (checksums.lisp:177-210, on the host: the blob's own check)
+  static uint32_t tab[256];
+  static std::once_flag once;
+  std::call_once(once, []() {
+    for (uint32_t i = 0; i < 256; i++) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; k++) c = (c & 1) ? (0xedb88320u ^ (c >> 1)) : (c >> 1);
+      tab[i] = c;
+    }
+  });
+  uint32_t c = 0xffffffffu;
+  for (size_t i = 0; i < n; i++) c = tab[(c ^ p[i]) & 0xff] ^ (c >> 8);
+  return c ^ 0xffffffffu;
+}
+
+// tbz_ix_copy over `recs` (offsets into src / dst), long records cut into pieces of IX_PIECE octets: a workgroup each.
+// src is one of the engine's own buffers (the kernel loads whole aligned 16-octet lines around a record)
+static int ix_copy(tbz_ctx* ctx, const void* src, void* dst, const std::vector<IxRec>& recs) {
+  std::vector<IxRec> pieces;
+  for (const IxRec& q : recs)
+    for (uint64_t o = 0; o < q.len; o += IX_PIECE) pieces.push_back(IxRec{q.src + o, q.dst + o, std::min<uint64_t>(IX_PIECE, q.len - o)});
+  if (pieces.empty()) return 0;
+  int r;
+  if ((r = upload(ctx, ctx->d_ix_recs, pieces))) return r;
+  constexpr size_t MAX_GRID = 1u << 23;  // (x 256 lanes: within a launch's 2^32 threads)
+  for (size_t a = 0; a < pieces.size(); a += MAX_GRID) {
+    const size_t cnt = std::min(MAX_GRID, pieces.size() - a);
+    IxCopyParams p{(const u8*)src, (u8*)dst, (const IxRec*)ctx->d_ix_recs.p + a, (u32)cnt};
+    TBZ_LAUNCH_WG(tbz_ix_copy, cnt, IX_THREADS, ctx->stream, p);
+  }
+  TBZ_HIP(hipGetLastError());
+  return 0;
+}
+
+// the windows' places in d_win
+static void ix_layout_windows(tbz_index* ix) {
+  const size_t n = ix->out_off.size();
+  ix->win_len.resize(n);
+  ix->win_off.resize(n);
+  uint64_t at = 0;
+  for (size_t k = 0; k < n; k++) {
+    ix->win_len[k] = (uint32_t)std::min<uint64_t>(ix->out_off[k], IX_WIN);
+    ix->win_off[k] = at;
+    at = (at + ix->win_len[k] + 15) & ~15ull;
+  }
+  ix->win_bytes = at;
+}
+
+// what a ranges call decodes: the merged spans of intervals [p, q) that cover its ranges
+struct IxSpan {
+  size_t p, q;             // points; q == n_points: to the end of the stream
+  uint64_t in_lo, in_hi;   // the span's input octets in the stream
+  uint64_t d_in_off;       // ... and where they lie from the call's device input base
+  uint64_t exp;            // octets it must decode to
+  uint64_t out_base = 0;   // where its output starts in the span scratch
+  int32_t status = TBZ_E_INTERNAL;
+  bool ok = false;
+};
+struct IxPlan {
+  std::vector<IxSpan> spans;         // ascending, apart by at least one whole interval: they share no input octet
+  std::vector<int64_t> span_of;      // per range: its span, -1 for a range of no octets
+  std::vector<uint64_t> out_len;     // per range, clipped at the end of the stream
+};
+static void ix_plan(const tbz_index* ix, size_t n, const uint64_t* offs, const uint64_t* lens, IxPlan& P) {
+  const size_t np = ix->out_off.size();
+  struct PQ { size_t p, q, i; };
+  std::vector<PQ> v;
+  P.span_of.assign(n, -1);
+  P.out_len.assign(n, 0);
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t off = offs[i];
+    const uint64_t ol = off >= ix->out_total ? 0 : std::min<uint64_t>(lens[i], ix->out_total - off);
+    P.out_len[i] = ol;
+    if (!ol) continue;
+    const size_t p = (size_t)(std::upper_bound(ix->out_off.begin(), ix->out_off.end(), off) - ix->out_off.begin()) - 1;
+    const size_t q = (size_t)(std::lower_bound(ix->out_off.begin(), ix->out_off.end(), off + ol) - ix->out_off.begin());
+    v.push_back(PQ{p, q, i});
+  }
+  std::sort(v.begin(), v.end(), [](const PQ& a, const PQ& b) { return a.p != b.p ? a.p < b.p : a.i < b.i; });
+  for (const PQ& e : v) {
+    // overlapping OR touching spans are merged: what stays apart is apart by a whole interval, i.e. by at least 64 input
+    // octets — the token pool is addressed by input position, so two streams of a call may not share an input octet
+    if (P.spans.empty() || e.p > P.spans.back().q) {
+      IxSpan s{};
+      s.p = e.p;
+      s.q = e.q;
+      P.spans.push_back(s);
+    } else {
+      P.spans.back().q = std::max(P.spans.back().q, e.q);
+    }
+    P.span_of[e.i] = (int64_t)P.spans.size() - 1;
+  }
+  for (IxSpan& s : P.spans) {
+    s.in_lo = ix->in_bit[s.p] / 8;
+    s.in_hi = s.q < np ? (ix->in_bit[s.q] + 7) / 8 : ix->in_len;
+    s.d_in_off = s.in_lo;
+    s.exp = (s.q < np ? ix->out_off[s.q] : ix->out_total) - ix->out_off[s.p];
+    s.status = TBZ_E_INTERNAL;
+    s.ok = false;
+  }
+}
+
+// decode the plan's spans (in consecutive sub-batches when their scratch would exceed the pool cap), check every
+// interval, deliver the ranges of the spans that are sound to d_out + out_offs[i], fill the results
+static int ix_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P, size_t n, const uint64_t* offs, void* d_out,
+                  const uint64_t* out_offs, tbz_result* results) {
+  const size_t np = ix->out_off.size(), ns = P.spans.size();
+  int r;
+  tbz_timings acc{};
+  size_t passes = 0;
+  for (size_t a = 0; a < ns;) {
+    // ---- the sub-batch [a, b): span scratch + the engine's pools (9 octets per input octet of the extent)
+    size_t b = a;
+    uint64_t top = 0, in_lo = ~0ull, in_hi = 0;
+    while (b < ns) {
+      IxSpan& s = P.spans[b];
+      const uint64_t base = ((top + 255) & ~255ull) + IX_WIN, top2 = base + s.exp + 256;
+      const uint64_t lo2 = std::min(in_lo, s.d_in_off), hi2 = std::max(in_hi, s.d_in_off + (s.in_hi - s.in_lo));
+      if (b > a && top2 + (hi2 - lo2) * 9 > ctx->pool_cap) break;
+      s.out_base = base;
+      top = top2;
+      in_lo = lo2;
+      in_hi = hi2;
+      b++;
+    }
+    const size_t m = b - a;
+    if ((r = ensure(ctx, ctx->d_ix_span, top + 64))) return r;
+    // ---- every span's window in front of its output
+    std::vector<IxRec> recs;
+    std::vector<uint64_t> io(m), il(m), oo(m), oc(m), hl(m);
+    std::vector<uint32_t> bo(m);
+    for (size_t k = 0; k < m; k++) {
+      const IxSpan& s = P.spans[a + k];
+      const uint64_t w = ix->win_len[s.p];
+      if (w) recs.push_back(IxRec{ix->win_off[s.p], s.out_base - w, w});
+      io[k] = s.d_in_off;
+      il[k] = s.in_hi - s.in_lo;
+      oo[k] = s.out_base;
+      oc[k] = s.exp;
+      hl[k] = w;
+      bo[k] = (uint32_t)(ix->in_bit[s.p] & 7);
+    }
+    if ((r = ix_copy(ctx, ix->d_win, ctx->d_ix_span.p, recs))) return r;
+    // ---- ONE engine call over the spans: raw deflate streams entered at their points
+    CoreOpts opt;
+    opt.start_bit_offs = bo.data();
+    opt.hist_lens = hl.data();
+    std::vector<tbz_result> sr(m);
+    if ((r = inflate_core(ctx, TBZ_FORMAT_DEFLATE, m, d_in, io.data(), il.data(), ctx->d_ix_span.p, oo.data(), oc.data(), sr.data(),
+                          false, &opt)))
+      return r;
+    {
+      const tbz_timings& t = ctx->tim;
+      acc.scan_ms += t.scan_ms; acc.huff_ms += t.huff_ms; acc.lz_ms += t.lz_ms; acc.cksum_ms += t.cksum_ms;
+      acc.total_ms += t.total_ms; acc.find_ms += t.find_ms; acc.resolve_ms += t.resolve_ms;
+      acc.huff_launches += t.huff_launches; acc.fixup_rounds += t.fixup_rounds; acc.token_words += t.token_words;
+      acc.n_segments += t.n_segments; acc.n_groups += t.n_groups; acc.n_candidates += t.n_candidates;
+      acc.n_hgroups += t.n_hgroups; acc.k1_gang = t.k1_gang; acc.k2_kinds |= t.k2_kinds;
+      acc.scratch_bytes = std::max(acc.scratch_bytes, t.scratch_bytes);
+      passes++;
+    }
+    // a span that ends before the stream does runs out of input exactly at its last point, with exactly the octets
+    // between its points; the last one finishes.  Anything else is damage.
+    std::vector<uint64_t> co, cl;
+    std::vector<uint32_t> init, want, sums;
+    std::vector<size_t> owner;
+    for (size_t k = 0; k < m; k++) {
+      IxSpan& s = P.spans[a + k];
+      const int32_t expect = s.q < np ? TBZ_INPUT_UNDERRUN : TBZ_FINISHED;
+      if (sr[k].status == expect && sr[k].out_total == s.exp && sr[k].out_len == s.exp) {
+        s.ok = true;
+        s.status = TBZ_FINISHED;
+        for (size_t j = s.p; j < s.q; j++) {
+          co.push_back(s.out_base + (ix->out_off[j] - ix->out_off[s.p]));
+          cl.push_back(ix->interval_end(j) - ix->out_off[j]);
+          init.push_back(0);
+          want.push_back(ix->crc[j]);
+          owner.push_back(a + k);
+        }
+      } else {
+        s.status = sr[k].status < 0 ? sr[k].status : TBZ_E_CRC32;
+      }
+    }
+    if (!co.empty()) {
+      if ((r = run_checksums(ctx, 2, ctx->d_ix_span.p, co, cl, init, sums))) return r;
+      for (size_t j = 0; j < co.size(); j++)
+        if ((cl[j] ? sums[j] : 0u) != want[j]) {
+          P.spans[owner[j]].ok = false;
+          P.spans[owner[j]].status = TBZ_E_CRC32;
+        }
+    }
+    // ---- only now the requested octets go to the caller
+    recs.clear();
+    for (size_t i = 0; i < n; i++) {
+      const int64_t si = P.span_of[i];
+      if (si < (int64_t)a || si >= (int64_t)b || !P.spans[si].ok) continue;
+      const IxSpan& s = P.spans[si];
+      recs.push_back(IxRec{s.out_base + (offs[i] - ix->out_off[s.p]), out_offs[i], P.out_len[i]});
+    }
+    if ((r = ix_copy(ctx, ctx->d_ix_span.p, d_out, recs))) return r;
+    TBZ_HIP(hipStreamSynchronize(ctx->stream));  // (the next sub-batch reuses the scratch and the record list)
+    a = b;
+  }
+  if (passes) {
+    acc.passes = passes > 1 ? (uint32_t)passes : 0u;
+    ctx->tim = acc;
+  } else {
+    ctx->tim = tbz_timings{};
+  }
+  for (size_t i = 0; i < n; i++) {
+    tbz_result& R = results[i];
+    memset(&R, 0, sizeof R);
+    R.status = TBZ_FINISHED;
+    R.out_total = ix->out_total;
+    const int64_t si = P.span_of[i];
+    if (si < 0) continue;
+    const IxSpan& s = P.spans[si];
+    R.status = s.ok ? TBZ_FINISHED : s.status;
+    R.out_len = s.ok ? P.out_len[i] : 0;
+    R.boundary_out = ix->out_off[s.p];
+    R.segments = (uint32_t)(s.q - s.p);
+    R.in_consumed = s.in_hi - s.in_lo;
+    R.flags = s.ok ? 1u : 0u;
+  }
+  return 0;
+}
+
+static int ix_check_args(tbz_ctx* ctx, const tbz_index* ix, size_t in_len, size_t n, const uint64_t* offs, const uint64_t* lens,
+                         const void* outs, tbz_result* results) {
+  if (!ctx || !ix || ix->ctx != ctx || (n && (!offs || !lens || !outs || !results))) return TBZ_E_ARG;
+  if (in_len != ix->in_len) return TBZ_E_ARG;
+  if (!ctx->sym_hist) return TBZ_E_UNSUPPORTED;  // (TBZ_HIST=off: no way to reach the window, as for a resumed session)
+  return 0;
+}
+}  // namespace tbz
+
+extern "C" {
+
+int tbz_index_build_device(tbz_ctx* ctx, int format, const void* d_in, size_t in_len, size_t spacing, tbz_index** out_index,
+                           tbz_result* res) {
+  using namespace tbz;
+  if (!ctx || !out_index || !res || format < 0 || format > 2 || (in_len && !d_in)) return TBZ_E_ARG;
+  *out_index = nullptr;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  // point 0: the first block's bit (the head item starts at the container header, not at a block)
+  uint64_t first_bit = format == TBZ_FORMAT_ZLIB ? 16 : 0;
+  bool first_known = true;
+  if (format == TBZ_FORMAT_GZIP) {
+    std::vector<uint8_t> head(std::min<size_t>(in_len, 70000));
+    if (!head.empty()) TBZ_HIP(hipMemcpy(head.data(), d_in, head.size(), hipMemcpyDeviceToHost));
+    tbz_gzip_header h;
+    tbz_gzip_header_parse(head.data(), head.size(), &h);
+    first_known = h.status == 0 && h.stage == 8;
+    first_bit = 8ull * h.header_len;
+  }
+  CoreOpts opt;
+  opt.want_points = true;
+  int alloc_err = 0;
+  opt.alloc = [&](uint64_t total) -> void* {
+    alloc_err = ensure(ctx, ctx->d_out_stage, total + 64);
+    return alloc_err ? nullptr : ctx->d_out_stage.p;
+  };
+  uint64_t io = 0, il = in_len, oo = 0, oc = 1ull << 62;
+  int r = inflate_core(ctx, format, 1, d_in, &io, &il, nullptr, &oo, &oc, res, false, &opt);
+  if (r) return alloc_err ? alloc_err : r;
+  if (res->status != TBZ_FINISHED) return 0;  // no index: res says why
+  if (!first_known) return TBZ_E_UNSUPPORTED;  // (a gzip header beyond the octets looked at)
+  const tbz_timings tim = ctx->tim;
+  const uint64_t total = res->out_total;
+  const uint64_t sp = spacing == 0 ? (1u << 20) : std::max<uint64_t>(spacing, IX_WIN);
+  tbz_index* ix = new tbz_index();
+  ix->ctx = ctx;
+  ix->format = format;
+  ix->in_len = in_len;
+  ix->out_total = total;
+  ix->first_block_bit = first_bit;
+  ix->check = format == TBZ_FORMAT_ZLIB ? res->adler32 : format == TBZ_FORMAT_GZIP ? res->crc32 : 0u;
+  ix->in_bit.push_back(first_bit);
+  ix->out_off.push_back(0);
+  for (const auto& pt : opt.points) {  // proven block starts, taken greedily
+    if (pt.first <= first_bit || pt.second >= total) continue;
+    if (pt.second < ix->out_off.back() + sp || pt.first < ix->in_bit.back() + IX_MIN_IN_BITS) continue;
+    ix->in_bit.push_back(pt.first);
+    ix->out_off.push_back(pt.second);
+  }
+  const size_t np = ix->out_off.size();
+  ix_layout_windows(ix);
+  auto fail = [&](int code) {
+    tbz_index_destroy(ix);
+    return code;
+  };
+  if (hipMalloc(&ix->d_win, ix->win_bytes + 64) != hipSuccess) {
+    (void)hipGetLastError();
+    ix->d_win = nullptr;
+    return fail(TBZ_E_NOMEM);
+  }
+  std::vector<IxRec> recs;
+  std::vector<uint64_t> co(np), cl(np);
+  std::vector<uint32_t> init(np, 0);
+  for (size_t k = 0; k < np; k++) {
+    if (ix->win_len[k]) recs.push_back(IxRec{ix->out_off[k] - ix->win_len[k], ix->win_off[k], ix->win_len[k]});
+    co[k] = ix->out_off[k];
+    cl[k] = ix->interval_end(k) - ix->out_off[k];
+  }
+  if ((r = ix_copy(ctx, ctx->d_out_stage.p, ix->d_win, recs))) return fail(r);
+  if ((r = run_checksums(ctx, 2, ctx->d_out_stage.p, co, cl, init, ix->crc))) return fail(r);
+  for (size_t k = 0; k < np; k++)
+    if (!cl[k]) ix->crc[k] = 0;
+  ctx->tim = tim;
+  *out_index = ix;
+  return 0;
+}
+
+int tbz_index_build(tbz_ctx* ctx, int format, const uint8_t* in, size_t in_len, size_t spacing, tbz_index** out_index,
+                    tbz_result* res) {
+  using namespace tbz;
+  if (!ctx || !out_index || !res || (in_len && !in)) return TBZ_E_ARG;
+  *out_index = nullptr;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  int r;
+  if ((r = ensure(ctx, ctx->d_in_stage, in_len + 64))) return r;
+  if ((r = stage_in(ctx, ctx->d_in_stage.p, in, in_len))) return r;
+  r = tbz_index_build_device(ctx, format, ctx->d_in_stage.p, in_len, spacing, out_index, res);
+  ctx->tim.h2d_copies = in_len ? 1u : 0u;
+  return r;
+}
+
+void tbz_index_destroy(tbz_index* ix) {
+  if (!ix) return;
+  if (ix->d_win && ix->ctx) {
+    hipSetDevice(ix->ctx->device);
+    hipStreamSynchronize(ix->ctx->stream);
+    hipFree(ix->d_win);
+  }
+  delete ix;
+}
+
+int tbz_index_info(const tbz_index* ix, int* format, size_t* in_len, size_t* out_total, size_t* n_points, size_t* max_interval) {
+  if (!ix) return TBZ_E_ARG;
+  if (format) *format = ix->format;
+  if (in_len) *in_len = (size_t)ix->in_len;
+  if (out_total) *out_total = (size_t)ix->out_total;
+  if (n_points) *n_points = ix->out_off.size();
+  if (max_interval) {
+    uint64_t mx = 0;
+    for (size_t k = 0; k < ix->out_off.size(); k++) mx = std::max(mx, ix->interval_end(k) - ix->out_off[k]);
+    *max_interval = (size_t)mx;
+  }
+  return 0;
+}
+
+int tbz_index_points(const tbz_index* ix, size_t max, uint64_t* in_bit, uint64_t* out_off) {
+  if (!ix || (max && (!in_bit || !out_off))) return TBZ_E_ARG;
+  const size_t k = std::min(max, ix->out_off.size());
+  for (size_t i = 0; i < k; i++) {
+    in_bit[i] = ix->in_bit[i];
+    out_off[i] = ix->out_off[i];
+  }
+  return (int)std::min<size_t>(k, 0x7fffffff);
+}
+
+// the blob, little-endian: u32 magic, version, format, check; u64 in_len, out_total, first_block_bit, n_points, window
+// octets; u64 in_bit[n]; u64 out_off[n]; u32 win_len[n]; u32 crc[n]; the windows, one after another; u32 crc32 of all that
+int tbz_index_export(const tbz_index* ix, uint8_t* buf, size_t cap, size_t* need) {
+  using namespace tbz;
+  if (!ix || !need) return TBZ_E_ARG;
+  tbz_ctx* ctx = ix->ctx;
+  const size_t np = ix->out_off.size();
+  uint64_t wsum = 0;
+  for (uint32_t w : ix->win_len) wsum += w;
+  const size_t size = IX_HEAD + np * 24 + (size_t)wsum + 4;
+  *need = size;
+  if (!buf) return 0;
+  if (cap < size) return TBZ_E_ARG;
+  uint8_t* p = buf;
+  auto put32 = [&](uint32_t v) { memcpy(p, &v, 4); p += 4; };
+  auto put64 = [&](uint64_t v) { memcpy(p, &v, 8); p += 8; };
+  put32(IX_MAGIC); put32(IX_VERSION); put32((uint32_t)ix->format); put32(ix->check);
+  put64(ix->in_len); put64(ix->out_total); put64(ix->first_block_bit); put64(np); put64(wsum);
+  for (uint64_t v : ix->in_bit) put64(v);
+  for (uint64_t v : ix->out_off) put64(v);
+  for (uint32_t v : ix->win_len) put32(v);
+  for (uint32_t v : ix->crc) put32(v);
+  if (wsum) {
+    TBZ_HIP(hipSetDevice(ctx->device));
+    std::vector<uint8_t> w(ix->win_bytes);
+    TBZ_HIP(hipStreamSynchronize(ctx->stream));
+    TBZ_HIP(hipMemcpy(w.data(), ix->d_win, w.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < np; k++) {
+      memcpy(p, w.data() + ix->win_off[k], ix->win_len[k]);
+      p += ix->win_len[k];
+    }
+  }
+  put32(ix_crc32(buf, (size_t)(p - buf)));
+  return 0;
+}
+
+int tbz_index_import(tbz_ctx* ctx, const uint8_t* buf, size_t len, tbz_index** out_index) {
+  using namespace tbz;
+  if (!ctx || !out_index) return TBZ_E_ARG;
+  *out_index = nullptr;
+  if (!buf || len < IX_HEAD + 24 + 4) return TBZ_E_ARG;
+  const uint8_t* p = buf;
+  auto get32 = [&]() { uint32_t v; memcpy(&v, p, 4); p += 4; return v; };
+  auto get64 = [&]() { uint64_t v; memcpy(&v, p, 8); p += 8; return v; };
+  if (get32() != IX_MAGIC || get32() != IX_VERSION) return TBZ_E_ARG;
+  const uint32_t format = get32(), check = get32();
+  const uint64_t in_len = get64(), out_total = get64(), first_bit = get64(), np = get64(), wsum = get64();
+  if (format > 2 || np == 0 || np > (len - IX_HEAD - 4) / 24) return TBZ_E_ARG;
+  if (wsum > len || IX_HEAD + np * 24 + wsum + 4 != len) return TBZ_E_ARG;  // the sizes add up
+  uint32_t stored;
+  memcpy(&stored, buf + len - 4, 4);
+  if (ix_crc32(buf, len - 4) != stored) return TBZ_E_ARG;
+  std::unique_ptr<tbz_index> ix(new tbz_index());
+  ix->format = (int)format;
+  ix->check = check;
+  ix->in_len = in_len;
+  ix->out_total = out_total;
+  ix->first_block_bit = first_bit;
+  ix->in_bit.resize(np);
+  ix->out_off.resize(np);
+  ix->crc.resize(np);
+  std::vector<uint32_t> wl(np);
+  for (auto& v : ix->in_bit) v = get64();
+  for (auto& v : ix->out_off) v = get64();
+  for (auto& v : wl) v = get32();
+  for (auto& v : ix->crc) v = get32();
+  // consistent in itself: point 0 where the first block is, both offsets ascending as the builder spaces them, every
+  // point inside the stream, every window exactly the octets in front of its point
+  if (ix->out_off[0] != 0 || ix->in_bit[0] != first_bit) return TBZ_E_ARG;
+  // ... and the first block where the format puts it: bit 0 (raw), 16 (zlib), behind a whole gzip header of 10 octets or more
+  if (format == TBZ_FORMAT_DEFLATE ? first_bit != 0 : format == TBZ_FORMAT_ZLIB ? first_bit != 16 : (first_bit < 80 || (first_bit & 7)))
+    return TBZ_E_ARG;
+  uint64_t wcount = 0;
+  for (size_t k = 0; k < np; k++) {
+    if (k && (ix->out_off[k] <= ix->out_off[k - 1] || ix->in_bit[k] < ix->in_bit[k - 1] + IX_MIN_IN_BITS)) return TBZ_E_ARG;
+    if (k && ix->out_off[k] >= out_total) return TBZ_E_ARG;
+    if (ix->in_bit[k] / 8 >= in_len) return TBZ_E_ARG;  // (every point inside the input: no stream of no octets finishes)
+    if (wl[k] != std::min<uint64_t>(ix->out_off[k], IX_WIN)) return TBZ_E_ARG;
+    wcount += wl[k];
+  }
+  if (wcount != wsum) return TBZ_E_ARG;
+  ix_layout_windows(ix.get());
+  std::vector<uint8_t> w(ix->win_bytes + 16, 0);
+  for (size_t k = 0; k < np; k++) {
+    memcpy(w.data() + ix->win_off[k], p, wl[k]);
+    p += wl[k];
+  }
+  TBZ_HIP(hipSetDevice(ctx->device));
+  void* d = nullptr;
+  if (hipMalloc(&d, ix->win_bytes + 64) != hipSuccess) {
+    (void)hipGetLastError();
+    return TBZ_E_NOMEM;
+  }
+  if (ix->win_bytes && hipMemcpy(d, w.data(), ix->win_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(d);
+    ctx->err = "hipMemcpy of the index windows failed";
+    return TBZ_E_HIP;
+  }
+  ix->d_win = d;
+  ix->ctx = ctx;
+  *out_index = ix.release();
+  return 0;
+}
+
+int tbz_inflate_ranges_device(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, size_t in_len, size_t n, const uint64_t* offs,
+                              const uint64_t* lens, void* d_out, const uint64_t* out_offs, tbz_result* results) {
+  using namespace tbz;
+  int r;
+  if ((r = ix_check_args(ctx, ix, in_len, n, offs, lens, out_offs, results))) return r;
+  if (in_len && !d_in) return TBZ_E_ARG;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  IxPlan P;
+  ix_plan(ix, n, offs, lens, P);
+  if (!P.spans.empty() && !d_out) return TBZ_E_ARG;
+  return ix_run(ctx, ix, d_in, P, n, offs, d_out, out_offs, results);
+}
+
+int tbz_inflate_ranges(tbz_ctx* ctx, const tbz_index* ix, const uint8_t* in, size_t in_len, size_t n, const uint64_t* offs,
+                       const uint64_t* lens, uint8_t* const* outs, tbz_result* results) {
+  using namespace tbz;
+  int r;
+  if ((r = ix_check_args(ctx, ix, in_len, n, offs, lens, outs, results))) return r;
+  if (in_len && !in) return TBZ_E_ARG;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  IxPlan P;
+  ix_plan(ix, n, offs, lens, P);
+  // only the spans' input octets go to the device, one after another ...
+  std::vector<StagePiece> pin;
+  uint64_t at = 0;
+  for (IxSpan& s : P.spans) {
+    s.d_in_off = at;
+    pin.push_back(StagePiece{(uint8_t*)in + s.in_lo, at, s.in_hi - s.in_lo});
+    at = (at + (s.in_hi - s.in_lo) + 15) & ~15ull;
+  }
+  if ((r = ensure(ctx, ctx->d_in_stage, at + 64))) return r;
+  if ((r = stage_in(ctx, ctx->d_in_stage.p, pin))) return r;
+  // ... and only the requested octets come back
+  std::vector<uint64_t> oo(n);
+  uint64_t ot = 0;
+  for (size_t i = 0; i < n; i++) {
+    oo[i] = ot;
+    ot = (ot + P.out_len[i] + 15) & ~15ull;
+  }
+  if ((r = ensure(ctx, ctx->d_out_stage, ot + 64))) return r;
+  if ((r = ix_run(ctx, ix, ctx->d_in_stage.p, P, n, offs, ctx->d_out_stage.p, oo.data(), results))) return r;
+  ctx->tim.h2d_copies = pin.empty() ? 0u : 1u;
+  std::vector<StagePiece> pout;
+  for (size_t i = 0; i < n; i++)
+    if (results[i].out_len) {
+      if (!outs[i]) return TBZ_E_ARG;
+      pout.push_back(StagePiece{outs[i], oo[i], results[i].out_len});
+    }
+  return stage_out(ctx, ctx->d_out_stage.p, pout);
 }
 
 }  // extern "C"

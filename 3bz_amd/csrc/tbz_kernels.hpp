@@ -130,7 +130,8 @@ struct K0Params {
   Item* items;            // item build out
   u32 format;
   u32 second_pass;        // items: the marker array was written by the emitting pass
-  u32 start_bit_off;      // stream 0's first block header sits at this bit of the stream's first octet (resumed streams)
+  const u32* start_bit_off;  // per stream (nullptr: all 0): the stream's first block header sits at this bit of its first octet
+                          // (resumed streams, spans entered at an index point)
   u32* n_fixed;           // items: [0] counts the marker items whose first block is a fixed-Huffman block (nullptr: not wanted) —
                           // where most are, the streams are fixed-Huffman territory and K0c looks for block chains inside them
   u32 resume;             // items: stream 0's head item carries ITEM_RESUME (a session's continuation inside a block)
@@ -298,7 +299,7 @@ TBZ_KERNEL void tbz_k0_items(K0Params P) {
   const u32 s = lo, fm = P.first_marker[s], nm = P.first_marker[s + 1] - fm;
   const u32 k = i - (fm + s);
   Item it;
-  it.start_bit = k == 0 ? P.str_off[s] * 8 + (s == 0 ? P.start_bit_off : 0u) : P.markers[fm + k - 1];
+  it.start_bit = k == 0 ? P.str_off[s] * 8 + (P.start_bit_off ? P.start_bit_off[s] : 0u) : P.markers[fm + k - 1];
   it.limit_bit = k < nm ? P.markers[fm + k] : ~0ull;
   it.end_byte = P.str_off[s] + P.str_len[s];
   it.stream = s;
@@ -459,7 +460,8 @@ struct K0bParams {
   u64* merged;             // ... and the merged list
   u32* first_merged;       //   [n_streams+1]
   u32* head_merged;        //   [2]: total, 0  (laid out as K0Params::head for tbz_k0_items)
-  u32 start_bit_off;       // stream 0 begins at this bit of its first octet: nothing before it is a candidate
+  const u32* start_bit_off;  // per stream (nullptr: all 0): the stream begins at this bit of its first octet: nothing before it
+                           // is a candidate
   u32 slots_per_tile;      // K0B_SLOTS for the dynamic-header finder, K0C_SLOTS for the fixed-chain finder
   u32 pair;                // tbz_k0b_validate: 1 = two tiles per wave (32 lanes each), for launches of many waves
   u64* ends;               // K0c: [n_tiles][slots_per_tile] where the block that starts at the slot's candidate ends (0: nowhere)
@@ -491,7 +493,7 @@ TBZ_KERNEL void tbz_k0b_scan(K0bParams P) {
   const uintptr_t s_lo = base + P.str_off[s], s_hi = s_lo + P.str_len[s];
   const uintptr_t t0 = (s_lo & ~(uintptr_t)15) + (uintptr_t)(tile - P.tile_first[s]) * K0B_TILE;
   // candidate bit positions p (relative to in_base) must satisfy p_min <= p <= p_max
-  const u64 p_min = (u64)(s_lo - base) * 8 + 1 + (s == 0 ? P.start_bit_off : 0u);  // (the stream's first bit belongs to the head item)
+  const u64 p_min = (u64)(s_lo - base) * 8 + 1 + (P.start_bit_off ? P.start_bit_off[s] : 0u);  // (the stream's first bit belongs to the head item)
   const u64 p_end = (u64)(s_hi - base) * 8;
   u64* slots = P.slots + (u64)tile * P.slots_per_tile;
   u32 nout = 0;
@@ -813,7 +815,7 @@ TBZ_KERNEL void tbz_k0b_space(K0bParams P) {
   const u32 s = k0b_find_stream(P, tile);
   const u64* slots = P.slots + (u64)tile * P.slots_per_tile;
   const u32 count = P.counts[tile];
-  const u64 head = P.str_off[s] * 8 + (s == 0 ? P.start_bit_off : 0u);
+  const u64 head = P.str_off[s] * 8 + (P.start_bit_off ? P.start_bit_off[s] : 0u);
   u64 carry = k0x_prev_tile_last(P, s, tile);
   u32 kept = 0;
   for (u32 j0 = 0; j0 < P.slots_per_tile; j0 += 64) {  // wave-uniform trip count; every mask word is written
@@ -850,7 +852,7 @@ TBZ_KERNEL void tbz_k0c_scan(K0bParams P) {
   const uintptr_t base = (uintptr_t)P.in_base;
   const uintptr_t s_lo = base + P.str_off[s], s_hi = s_lo + P.str_len[s];
   const uintptr_t t0 = (s_lo & ~(uintptr_t)15) + (uintptr_t)(tile - P.tile_first[s]) * K0C_TILE;
-  const u64 p_min = (u64)(s_lo - base) * 8 + 8 + (s == 0 ? P.start_bit_off : 0u);
+  const u64 p_min = (u64)(s_lo - base) * 8 + 8 + (P.start_bit_off ? P.start_bit_off[s] : 0u);
   const u64 p_end = (u64)(s_hi - base) * 8;
   u64* slots = P.slots + (u64)tile * P.slots_per_tile;
   u32 nout = 0;
@@ -1005,7 +1007,7 @@ TBZ_KERNEL void tbz_k0c_filter(K0bParams P) {
   const u64* slots = P.slots + (u64)tile * P.slots_per_tile;
   const u8* link = P.link + (u64)tile * P.slots_per_tile * 2;
   const u32 count = P.counts[tile];
-  const u64 head = P.str_off[s] * 8 + (s == 0 ? P.start_bit_off : 0u);
+  const u64 head = P.str_off[s] * 8 + (P.start_bit_off ? P.start_bit_off[s] : 0u);
   u64 carry = k0x_prev_tile_last(P, s, tile);
   u32 kept = 0;
   for (u32 j0 = 0; j0 < P.slots_per_tile; j0 += 64) {  // wave-uniform trip count; every mask word is written
@@ -5679,5 +5681,80 @@ TBZ_KERNEL_OCC(2) void tbz_small_fused(SmallParams P) {
   }
   leave(SMALL_DONE, check, 0);
 }
+
+
+// ================================================================================================
+// KX — tbz_ix_copy: batched segmented copy between device buffers (the seek index: capture the 32 KiB windows when an
+// index is built, place each span's window in front of its output before a range decode, deliver the requested octets
+// to the caller's buffer).  3bz has no counterpart (decompress-vector's :start / :end select INPUT, api.lisp:23-29).
+// One workgroup of four waves per piece; the host cuts long records into pieces of at most IX_PIECE octets, so one
+// long range is spread over the whole chip.  Source and destination alignment are arbitrary and independent:
+//   head   the octets up to the destination's next 16-octet boundary, one per lane
+//   body   16 octets per lane and step, one aligned 16-octet store.  Source 16-aligned at that point: one aligned
+//          16-octet load.  Otherwise the two aligned 16-octet lines that hold the octets are loaded (the second is
+//          the next lane's first: one HBM fetch, the other a hit) and realigned with v_alignbit over their eight words;
+//          the misalignment is the same for every step of a piece, so the word selection is a wave-uniform switch
+//          with constant register indices (no scratch)
+//   tail   the last < 16 octets, one per lane
+// A record's source must come from one of the engine's own buffers (16-aligned allocations with at least 16 octets of
+// slack behind the last octet): the aligned lines the body loads may begin before the record and end behind it.
+// Nothing outside [dst, dst + len) is written.
+// ================================================================================================
+struct IxRec {
+  u64 src, dst;  // octet offsets in src_base / dst_base
+  u64 len;
+};
+struct IxCopyParams {
+  const u8* src_base;
+  u8* dst_base;
+  const IxRec* recs;
+  u32 n_recs;
+};
+constexpr u32 IX_PIECE = 64u << 10;  // octets per workgroup: 16 steps of 256 lanes x 16 octets
+constexpr u32 IX_THREADS = 256;
+
+#define TBZ_IX_REALIGN(W0, W1, W2, W3, W4) \
+  o.x = tbz_alignbit(W1, W0, sh);          \
+  o.y = tbz_alignbit(W2, W1, sh);          \
+  o.z = tbz_alignbit(W3, W2, sh);          \
+  o.w = tbz_alignbit(W4, W3, sh);
+
+TBZ_KERNEL_WG(256, 1) void tbz_ix_copy(IxCopyParams P) {
+  const u32 r = tbz_block();
+  if (r >= P.n_recs) return;
+  const u32 t = tbz_wave() * 64 + tbz_lane();
+  const IxRec R = P.recs[r];
+  const u8* TBZ_RESTRICT s = P.src_base + R.src;
+  u8* TBZ_RESTRICT d = P.dst_base + R.dst;
+  const u64 n = R.len;
+  const u64 head = n < (u64)((0 - (uintptr_t)d) & 15) ? n : (u64)((0 - (uintptr_t)d) & 15);
+  if (t < head) d[t] = s[t];
+  const u64 units = (n - head) >> 4;
+  const u8* sb = s + head;
+  u8* db = d + head;
+  const u32 k = (u32)((uintptr_t)sb & 15);  // (the same for every step: both sides advance by 16)
+  if (k == 0) {
+    for (u64 u = t; u < units; u += IX_THREADS) *(tbz_u32x4*)(db + u * 16) = *(const tbz_u32x4*)(sb + u * 16);
+  } else {
+    const u8* al = sb - k;
+    const u32 sh = (k & 3) * 8;
+    const u32 wo = k >> 2;
+    for (u64 u = t; u < units; u += IX_THREADS) {
+      const tbz_u32x4 a = *(const tbz_u32x4*)(al + u * 16);
+      const tbz_u32x4 b = *(const tbz_u32x4*)(al + u * 16 + 16);
+      tbz_u32x4 o;
+      switch (wo) {
+        case 0: TBZ_IX_REALIGN(a.x, a.y, a.z, a.w, b.x) break;
+        case 1: TBZ_IX_REALIGN(a.y, a.z, a.w, b.x, b.y) break;
+        case 2: TBZ_IX_REALIGN(a.z, a.w, b.x, b.y, b.z) break;
+        default: TBZ_IX_REALIGN(a.w, b.x, b.y, b.z, b.w) break;
+      }
+      *(tbz_u32x4*)(db + u * 16) = o;
+    }
+  }
+  const u64 done = head + units * 16;
+  if (t < n - done) d[done + t] = s[done + t];
+}
+#undef TBZ_IX_REALIGN
 
 }  // namespace tbz

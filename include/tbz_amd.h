@@ -281,6 +281,60 @@ int tbz_session_decompress(tbz_session* s, uint8_t* out, size_t out_cap, tbz_res
  * after a resume are counted again: in_decoded / octets fed is the re-decode factor) */
 int tbz_session_stats(const tbz_session* s, uint64_t* n_decodes, uint64_t* in_decoded);
 
+/* ---- seek index and byte-range decode: random access into ONE stream ------------------------------
+ * (Additive: TBZ_ABI_VERSION stays 4 — nothing that existed changes its signature, layout or result.)
+ * The nearest thing in the reference is (decompress-vector v :start s :end e), api.lisp:23-29 — but :start / :end
+ * select INPUT octets, and a deflate stream can only be decoded from its first block (deflate.lisp:719-722); 3bz has no
+ * way to ask for output octets [off, off + len).  An index keeps what the engine proves anyway while it decodes a
+ * stream once: block starts (bit position in the input, octets of output before it) at least `spacing` output octets
+ * and 64 input octets apart, the 32 KiB of output in front of each (the window, deflate.lisp:343-352), and a crc32 of
+ * every interval between two points.  spacing 0 = 1 MiB; values below 32 KiB are raised to 32 KiB.  Granularity is what
+ * the engine can prove: a stream in which no inner block start is found (long chains of stored blocks) has point 0
+ * only, and ranges are still served from there at the cost of the prefix; tbz_index_info's max_interval tells.
+ * Point 0 is (first block's bit, 0): bit 0 for raw deflate, 16 for zlib, 8 * tbz_gzip_header.header_len for gzip.
+ * A stream that does not decode to TBZ_FINISHED (a trailer mismatch included) yields no index: *out_index = NULL, the
+ * call returns 0 and res->status says why.  An index is bound to the context it was built or imported on and is
+ * released with tbz_index_destroy before that context is. */
+typedef struct tbz_index tbz_index;
+int tbz_index_build_device(tbz_ctx* ctx, int format, const void* d_in, size_t in_len, size_t spacing, tbz_index** out_index,
+                           tbz_result* res);
+int tbz_index_build(tbz_ctx* ctx, int format, const uint8_t* in, size_t in_len, size_t spacing, tbz_index** out_index,
+                    tbz_result* res);
+void tbz_index_destroy(tbz_index* index);
+/* any out-pointer may be NULL.  max_interval: the largest distance between two successive points (or the last point
+ * and the end) in output octets — what a one-octet read costs at worst */
+int tbz_index_info(const tbz_index* index, int* format, size_t* in_len, size_t* out_total, size_t* n_points,
+                   size_t* max_interval);
+/* the first min(max, n_points) points; returns how many were written (or TBZ_E_ARG) */
+int tbz_index_points(const tbz_index* index, size_t max, uint64_t* in_bit, uint64_t* out_off);
+/* The index as octets, usable in another process and on another device: magic, version, the scalar fields, the point
+ * arrays, the interval crcs, the windows, and a crc32 over all of it.  *need = its size; buf NULL: size only; cap too
+ * small: TBZ_E_ARG.  tbz_index_import returns TBZ_E_ARG (and *out_index = NULL) for a blob that is short, of a wrong
+ * magic or version, inconsistent in itself (points not ascending or outside the stream, a first block where the format
+ * cannot have it, windows that are not the octets in front of their points, sizes that do not add up), or that fails its
+ * own crc.  An imported index may hold points closer than 32 KiB of output, with shorter windows; ranges work the same. */
+int tbz_index_export(const tbz_index* index, uint8_t* buf, size_t cap, size_t* need);
+int tbz_index_import(tbz_ctx* ctx, const uint8_t* buf, size_t len, tbz_index** out_index);
+/* n ranges (offs[i], lens[i]) of the stream's OUTPUT in one call.  Each range is served by the span of intervals that
+ * covers it; spans that overlap or touch are merged; all spans are decoded as raw deflate streams of ONE engine call,
+ * each entered at its point's bit with the point's window in front of its output; every interval decoded is checked
+ * against its crc32; then the requested octets go to d_out + out_offs[i] (host variant: outs[i]).  results[i]: status
+ * TBZ_FINISHED or the span's error (the decode's TBZ_E_*, or TBZ_E_CRC32 for a span that decodes to other octets than
+ * the index recorded: then out_len = 0 and nothing is written for the range; ranges of other spans are unaffected);
+ * out_len = min(len, out_total - off), 0 when off >= out_total (clipped at the end like read(2)); out_total = the
+ * stream's size; boundary_out = out_off of the point the span started from; segments = intervals the span decoded;
+ * in_consumed = input octets the span read; flags bit0 = interval checksums verified.  in_len other than the index's:
+ * TBZ_E_ARG.  TBZ_E_UNSUPPORTED with TBZ_HIST=off, as for a resumed session.  The host variant moves only the spans'
+ * input octets to the device and only the requested octets back.  Device scratch of a call: the spans' output plus 9 octets
+ * per input octet between the first span's first and the last span's last octet AS THEY LIE IN THE CALL'S INPUT — the host
+ * variant packs them, the device variant reads the stream in place, so ranges far apart in a large device-resident stream
+ * cost scratch in proportion to their distance (tbz_ctx_trim releases it). */
+int tbz_inflate_ranges_device(tbz_ctx* ctx, const tbz_index* index, const void* d_in, size_t in_len, size_t n,
+                              const uint64_t* offs, const uint64_t* lens, void* d_out, const uint64_t* out_offs,
+                              tbz_result* results);
+int tbz_inflate_ranges(tbz_ctx* ctx, const tbz_index* index, const uint8_t* in, size_t in_len, size_t n,
+                       const uint64_t* offs, const uint64_t* lens, uint8_t* const* outs, tbz_result* results);
+
 /* ---- gzip header metadata (host side; no device involved) --------------------------------------
  * What decompress-gzip leaves in the gzip-state's slots while it reads the header (gzip.lisp:110-266:
  * compression-method, flags, mtime, compression level, operating system, extra / name / comment fields, header CRC).

@@ -37,6 +37,8 @@
    #:*engine* #:open-engine #:close-engine #:with-engine #:trim-engine
    ;; ---- beyond the reference (SURVEY §8f-4): every member of a multi-member .gz
    #:decompress-gzip-members
+   ;; ---- beyond the reference (its :start / :end select INPUT, api.lisp:23-29): random access into one stream
+   #:build-index #:free-index #:decompress-range
    ;; ---- beyond the reference (SURVEY §8e): many independent streams over the GPUs of one node, from ONE Lisp process
    #:*engines* #:open-engines #:close-engines #:decompress-vectors))
 (in-package #:3bz-amd)
@@ -99,6 +101,26 @@
 (cffi:defcfun ("tbz_inflate_sharded_multi" %inflate-sharded-multi) :int
   (ctxs :pointer) (n-ctx :size) (format :int) (in :pointer) (in-len :size) (out :pointer) (out-cap :size) (res :pointer)
   (sharded :pointer))
+
+;;; seek index and byte-range decode (include/tbz_amd.h): the proven block starts of one stream, kept; a range of its
+;;; OUTPUT is served by decoding only the intervals that cover it
+(cffi:defcfun ("tbz_index_build" %index-build) :int
+  (ctx :pointer) (format :int) (in :pointer) (in-len :size) (spacing :size) (out-index :pointer) (res :pointer))
+(cffi:defcfun ("tbz_index_build_device" %index-build-device) :int
+  (ctx :pointer) (format :int) (d-in :pointer) (in-len :size) (spacing :size) (out-index :pointer) (res :pointer))
+(cffi:defcfun ("tbz_index_destroy" %index-destroy) :void (index :pointer))
+(cffi:defcfun ("tbz_index_info" %index-info) :int
+  (index :pointer) (format :pointer) (in-len :pointer) (out-total :pointer) (n-points :pointer) (max-interval :pointer))
+(cffi:defcfun ("tbz_index_points" %index-points) :int
+  (index :pointer) (max :size) (in-bit :pointer) (out-off :pointer))
+(cffi:defcfun ("tbz_index_export" %index-export) :int (index :pointer) (buf :pointer) (cap :size) (need :pointer))
+(cffi:defcfun ("tbz_index_import" %index-import) :int (ctx :pointer) (buf :pointer) (len :size) (out-index :pointer))
+(cffi:defcfun ("tbz_inflate_ranges" %inflate-ranges) :int
+  (ctx :pointer) (index :pointer) (in :pointer) (in-len :size) (n :size) (offs :pointer) (lens :pointer) (outs :pointer)
+  (results :pointer))
+(cffi:defcfun ("tbz_inflate_ranges_device" %inflate-ranges-device) :int
+  (ctx :pointer) (index :pointer) (d-in :pointer) (in-len :size) (n :size) (offs :pointer) (lens :pointer) (d-out :pointer)
+  (out-offs :pointer) (results :pointer))
 
 (deftype octet () '(unsigned-byte 8))
 (deftype octet-vector () '(simple-array octet (*)))
@@ -372,6 +394,38 @@
                                    (make-array 0 :element-type 'octet)))))))
         (check (cffi:foreign-slot-value res '(:struct tbz-result) 'status))
         (values output (cffi:foreign-slot-value res '(:struct tbz-result) 'out-len))))))
+
+;;; ---- random access (no counterpart in 3bz: a stream is decoded from its first block, deflate.lisp:719-722) ----
+(defun build-index (compressed &key (format :zlib) (spacing 0))
+  "Decodes COMPRESSED once and returns an index (a foreign pointer; FREE-INDEX releases it): block starts at least SPACING
+octets of output apart (0: 1 MiB), their 32 KiB windows and a crc32 per interval.  A stream that DECOMPRESS-VECTOR would
+not accept signals what DECOMPRESS-VECTOR signals."
+  (cffi:with-foreign-objects ((res '(:struct tbz-result)) (out :pointer))
+    (cffi:with-pointer-to-vector-data (pin compressed)
+      (check-call (%index-build (engine) (format-code format) pin (length compressed) spacing out res) "tbz_index_build"))
+    (let ((status (cffi:foreign-slot-value res '(:struct tbz-result) 'status)))
+      (when (minusp status) (error "~a" (%strerror status)))
+      (unless (zerop status) (error "incomplete ~a stream" format)))
+    (cffi:mem-ref out :pointer)))
+
+(defun free-index (index)
+  (%index-destroy index))
+
+(defun decompress-range (compressed index start end)
+  "Octets [START, END) of the stream's OUTPUT, as a fresh octet vector (clipped at the end of the stream).  Only the
+intervals of INDEX that cover the range are decoded, and only their input octets go to the device."
+  (let ((buffer (make-array (max 0 (- end start)) :element-type 'octet)))
+    (cffi:with-foreign-objects ((res '(:struct tbz-result)) (off :uint64) (len :uint64) (outs :pointer))
+      (setf (cffi:mem-ref off :uint64) start
+            (cffi:mem-ref len :uint64) (length buffer))
+      (cffi:with-pointer-to-vector-data (pin compressed)
+        (cffi:with-pointer-to-vector-data (pout buffer)
+          (setf (cffi:mem-ref outs :pointer) pout)
+          (check-call (%inflate-ranges (engine) index pin (length compressed) 1 off len outs res) "tbz_inflate_ranges")))
+      (let ((status (cffi:foreign-slot-value res '(:struct tbz-result) 'status))
+            (count (cffi:foreign-slot-value res '(:struct tbz-result) 'out-len)))
+        (when (minusp status) (error "~a" (%strerror status)))
+        (if (= count (length buffer)) buffer (subseq buffer 0 count))))))
 
 ;;; ---- every member of a multi-member .gz (SURVEY §8f-4; 3bz stops after the first: gzip.lisp:277-286) ----
 (defun decompress-gzip-members (compressed &key (start 0) (end (length compressed)) (max-members 1048576))
