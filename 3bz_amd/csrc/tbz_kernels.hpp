@@ -3526,6 +3526,10 @@ TBZ_K1G_KERNEL(64, 4)
 // initialise), and a far source comes from the plane's own flushed output.  (Both planes in one workgroup — two rings
 // moved by the same copies — was built and measured: 26.6 KB of LDS, six workgroups per CU, 8.4 ms per GiB against
 // 6.4 ms for two passes at ten per CU: profiles/README.md.)
+//
+// The resolve step, in the order of the file: k2_copy_coop (one match, all lanes); k2_short_store / k2_short_copy /
+// k2_short_octets (one match, its own lane); k2_far_round (round 0 of the ring kernels); k2_rounds (the one round loop,
+// both windows); k2_resolve, the driver over the two.
 // ================================================================================================
 constexpr u32 ADLER_P = 65521;
 #ifndef TBZ_EXP_K2R_SPAN  // (experiments: hipcc -DTBZ_EXP_K2R_SPAN=768 -DTBZ_EXP_K2R_HIST=4096 -DTBZ_EXP_K2R_FLUSH=1024 ...)
@@ -3716,171 +3720,137 @@ TBZ_DEV void k2_copy_coop(const K2Src& S, u32 rpos, u64 gpos, i64 d, u32 rd, u32
   }
 }
 
-// Multi-round resolution of one batch's matches (at most one per lane).  `pend` = lanes holding an
-// unresolved match; dofs = octet offset of the match inside the batch, whose first octet (group-relative offset gpos)
-// sits at window index rpos.  A match is ready when the part of its source that it does not produce itself
-// lies below the high-water mark (the offset of the first unresolved match; everything below is
-// final).  The first unresolved match is always ready, so every round makes progress.
-// RING: matches that copy from the flushed output or from computed pointers depend on nothing in flight: they go
-// first, all at once (one memory round trip per batch that has any).
-// STAGE (ring kernels on three waves, tbz_k2_lz77_ring3): K2_FAR = that first round only, K2_NEAR = everything after it
-// (the far round was another wave's, one batch earlier: its memory round trip is off the resolving wave's path).
-constexpr u32 K2_ALL = 0, K2_FAR = 1, K2_NEAR = 2;
-template <class W, u32 STAGE = K2_ALL>
-TBZ_DEV void k2_resolve(const K2Src& S, u64 pend, u32 rpos, u64 gpos, u32 dofs, u32 len, u32 dist) {
-  constexpr bool LINEAR = W::LINEAR;
-  static_assert(STAGE == K2_ALL || !LINEAR, "stages are the ring kernels'");
-  constexpr u32 RW = LINEAR ? 1u : W::RW;
+// ---- a short match (up to K2_SHORT octets), copied by its own lane.  Whatever their source, its octets travel as A0, A1
+// (the first sixteen) and B0, B1 (the last sixteen; up to sixteen octets: B1 alone, the last eight; up to eight: A0 alone).
+// The store half: octet-addressed wide LDS accesses, (overlapping) writes that cover exactly [rd, rd + len)
+TBZ_DEV void k2_short_store(u8* win, u32 rd, u32 len, u64 A0, u64 A1, u64 B0, u64 B1) {
+  if (len >= 17) {
+    k2_st64(win + rd, A0);
+    k2_st64(win + rd + 8, A1);
+    k2_st64(win + rd + len - 16, B0);
+    k2_st64(win + rd + len - 8, B1);
+  } else if (len >= 9) {
+    k2_st64(win + rd, A0);
+    k2_st64(win + rd + len - 8, B1);
+  } else if (len >= 4) {
+    k2_st32(win + rd, (u32)A0);
+    k2_st32(win + rd + len - 4, (u32)(A0 >> ((len - 4) * 8)));
+  } else {
+    k2_st16(win + rd, (u32)A0);
+    win[rd + 2] = (u8)(A0 >> 16);
+  }
+}
+// A source inside the window, disjoint from the destination (dist >= len): one or two reads for most matches, then the
+// same stores (four 8-octet accesses each way at most: a 16-octet struct copy took a round trip through scratch memory
+// here).  Each class loads, then calls the store ladder with a length the compiler knows the class of: after inlining
+// the inner ladder folds to that class's stores, so the compiled code walks the length classes once.  (Loading in one
+// ladder and storing in a second one — a load half of its own — was measured: every lane takes the divergent branches
+// twice per round, K2 13 % slower on the linear and the plain ring groups; profiles/README.md.)
+TBZ_DEV void k2_short_copy(u8* win, u32 rs, u32 rd, u32 len) {
+  if (len >= 17) {
+    const u64 a0 = k2_ld64(win + rs), a1 = k2_ld64(win + rs + 8);
+    const u64 b0 = k2_ld64(win + rs + len - 16), b1 = k2_ld64(win + rs + len - 8);
+    k2_short_store(win, rd, len, a0, a1, b0, b1);
+  } else if (len >= 9) {
+    k2_short_store(win, rd, len, k2_ld64(win + rs), 0, 0, k2_ld64(win + rs + len - 8));
+  } else if (len >= 4) {
+    k2_short_store(win, rd, len, k2_ld64(win + rs), 0, 0, 0);
+  } else {
+    k2_short_store(win, rd, len, k2_ld32(win + rs), 0, 0, 0);
+  }
+}
+// Octet by octet: overlapping (the match repeats its dist-octet pattern, all of it final already) or at the ring's seam
+template <class W>
+TBZ_DEV void k2_short_octets(u8* win, u32 rs, u32 rd, u32 len, u32 dist) {
+  u32 jj = 0;
+  for (u32 j = 0; j < len; j++) {
+    win[ring<W>(rd + j)] = win[ring<W>(rs + jj)];
+    jj = jj + 1 == dist ? 0 : jj + 1;
+  }
+}
+
+// RING, round 0: matches whose sources lie outside the window.  far: wholly in the flushed output; symall: wholly before
+// the group (computed pointers).  They depend on nothing in flight, so they go first, all at once (one memory round trip
+// per batch that has any).  Returns the lanes it settles — with COPY = false it only names them, the copies were another
+// wave's — and, in `oddm`, the lanes whose source straddles the group's start (or an invalid stream's distance): those
+// are copied one by one in the rounds.
+template <class W, bool COPY>
+TBZ_DEV u64 k2_far_round(const K2Src& S, u64 pend, u32 rpos, u64 gpos, u32 dofs, u32 len, u32 dist, bool mine, u32 rd, i64 s,
+                         u64& oddm) {
+  constexpr u32 RW = W::RW;
   u8* win = S.win;
-  const bool SYM = !LINEAR && S.hist != 0;  // (wave-uniform)
+  const bool SYM = S.hist != 0;  // (wave-uniform)
+  const bool symall = SYM && s + (i64)len <= 0;
+  const bool far = !symall && dist > W::HIST && s >= 0;
+  const bool odd = mine && !symall && !far && (dist > W::HIST || (SYM && s < 0));
+  const bool wide = len <= K2_SHORT && rd + 32 <= RW;
+  const u64 farm = tbz_ballot(mine && far), symm = tbz_ballot(mine && symall);
+  oddm = tbz_ballot(odd);
+  if (!COPY || !(farm | symm)) return farm | symm;
+  const bool fw = mine && wide && (far || symall);
+  u64 A0 = 0, A1 = 0, B0 = 0, B1 = 0;
+  const u64 m17 = tbz_ballot(fw && far && len >= 17);
+  if (fw && far) {
+    // sixteen octets from the match's first octet for everyone, the last sixteen for the matches longer than that
+    // (one load instruction per batch, mostly)
+    const u8* p = S.g0 + s;
+    tbz_u32x4 L0, L1;
+    tbz_gload128x2(p, p + len - 16, m17, L0, L1);
+    const u64 lo = ((u64)L0.y << 32) | L0.x, hi = ((u64)L0.w << 32) | L0.z;
+    A0 = lo;
+    if (len >= 17) {
+      A1 = hi;
+      B0 = ((u64)L1.y << 32) | L1.x;
+      B1 = ((u64)L1.w << 32) | L1.z;
+    } else if (len >= 9) {  // octets [len - 8, len) of the sixteen
+      const u32 sh = (len - 8) * 8;  // 8 .. 64
+      B1 = sh == 64 ? hi : ((lo >> sh) | (hi << (64 - sh)));
+    }
+  }
+  if (fw && symall) {  // computed pointers: the octet plane out of the identity table, the mark plane in arithmetic
+    const u32 q = (u32)(32768 + s);
+    if (S.plane) {
+      A0 = k2_mark8(q);
+      if (len >= 9) B1 = k2_mark8(q + len - 8);
+      if (len >= 17) {
+        A1 = k2_mark8(q + 8);
+        B0 = k2_mark8(q + len - 16);
+      }
+    } else {
+      A0 = k2_ld64(S.idt + (q & 255));
+      if (len >= 9) B1 = k2_ld64(S.idt + ((q + len - 8) & 255));
+      if (len >= 17) {
+        A1 = k2_ld64(S.idt + ((q + 8) & 255));
+        B0 = k2_ld64(S.idt + ((q + len - 16) & 255));
+      }
+    }
+  }
+  if (fw) k2_short_store(win, rd, len, A0, A1, B0, B1);
+  // the rest of them (long, or at the ring's seam): one at a time, all lanes
+  u64 rest = (farm | symm) & ~tbz_ballot(fw);
+  while (rest) {
+    const u32 i = (u32)tbz_ffs64(rest) - 1;
+    rest &= rest - 1;
+    const u32 di = tbz_readlane(dofs, i);
+    k2_copy_coop<W>(S, rpos, gpos, (i64)gpos + di, tbz_readlane(rd, i), tbz_readlane(dist, i), tbz_readlane(len, i));
+  }
+  tbz_sync();
+  return farm | symm;
+}
+
+// The rounds.  A match is ready when the part of its source that it does not produce itself lies below the high-water
+// mark (the offset of the first unresolved match; everything below is final).  The first unresolved match is always
+// ready, so every round makes progress.  `oddq` (RING; constant zero for the linear window): matches whose source
+// straddles the group's first octet wait their turn like any other (their part inside the group must be final), then
+// take the octet-by-octet path.  (The lane's values arrive as plain parameters: a per-lane record passed by reference
+// was tried and raised the ring kernels' scalar spills; profiles/README.md.)
+template <class W>
+TBZ_DEV void k2_rounds(const K2Src& S, u64 pend, u64 oddq, u32 rpos, u64 gpos, u32 dofs, u32 len, u32 dist, u32 rd, u32 rs, i32 need,
+                       bool fastable, u64 longm) {
+  constexpr bool LINEAR = W::LINEAR;
+  u8* win = S.win;
   const u32 lane = tbz_lane();
   const u64 lane_bit = 1ull << lane;
-  // the part of the source a match does not write itself ends at dofs - dist + min(len, dist)
-  const i32 need = (i32)dofs - (i32)dist + (i32)(len < dist ? len : dist);
-  const u32 rd = ring<W>(rpos + dofs);
-  const u32 rs = LINEAR ? (rd >= dist ? rd - dist : 0) : (rd >= dist % RW ? rd - dist % RW : rd + RW - dist % RW);
-  const u64 longm = tbz_ballot(len > K2_SHORT);
-  const i64 d = (i64)gpos + dofs, s = d - (i64)dist;
-  const bool mine = (pend & lane_bit) != 0;
-  tbz_sync();
-  if (!LINEAR) {
-    // ---- round 0: sources outside the window.  far: wholly in the flushed output; symall: wholly before the group
-    const bool symall = SYM && s + (i64)len <= 0;
-    const bool far = !symall && dist > W::HIST && s >= 0;
-    // straddles the group's start (or an invalid stream's distance): one by one
-    const bool odd = mine && !symall && !far && (dist > W::HIST || (SYM && s < 0));
-    const bool wide = len <= K2_SHORT && rd + 32 <= RW;
-    const u64 farm = tbz_ballot(mine && far), symm = tbz_ballot(mine && symall), oddm = tbz_ballot(odd);
-    if (STAGE == K2_NEAR) {
-      pend &= ~(farm | symm);
-    } else if (farm | symm) {
-      const bool fw = mine && wide && (far || symall);
-      u64 A0 = 0, A1 = 0, B0 = 0, B1 = 0;
-      const u64 m17 = tbz_ballot(fw && far && len >= 17);
-      if (fw && far) {
-        // sixteen octets from the match's first octet for everyone, the last sixteen for the matches longer than that
-        // (one load instruction per batch, mostly)
-        const u8* p = S.g0 + s;
-        tbz_u32x4 L0, L1;
-        tbz_gload128x2(p, p + len - 16, m17, L0, L1);
-        const u64 lo = ((u64)L0.y << 32) | L0.x, hi = ((u64)L0.w << 32) | L0.z;
-        A0 = lo;
-        if (len >= 17) {
-          A1 = hi;
-          B0 = ((u64)L1.y << 32) | L1.x;
-          B1 = ((u64)L1.w << 32) | L1.z;
-        } else if (len >= 9) {  // octets [len - 8, len) of the sixteen
-          const u32 sh = (len - 8) * 8;  // 8 .. 64
-          B1 = sh == 64 ? hi : ((lo >> sh) | (hi << (64 - sh)));
-        }
-      }
-      if (fw && symall) {  // computed pointers: the octet plane out of the identity table, the mark plane in arithmetic
-        const u32 q = (u32)(32768 + s);
-        if (S.plane) {
-          A0 = k2_mark8(q);
-          if (len >= 9) B1 = k2_mark8(q + len - 8);
-          if (len >= 17) {
-            A1 = k2_mark8(q + 8);
-            B0 = k2_mark8(q + len - 16);
-          }
-        } else {
-          A0 = k2_ld64(S.idt + (q & 255));
-          if (len >= 9) B1 = k2_ld64(S.idt + ((q + len - 8) & 255));
-          if (len >= 17) {
-            A1 = k2_ld64(S.idt + ((q + 8) & 255));
-            B0 = k2_ld64(S.idt + ((q + len - 16) & 255));
-          }
-        }
-      }
-      if (fw) {
-        if (len >= 17) {
-          k2_st64(win + rd, A0);
-          k2_st64(win + rd + 8, A1);
-          k2_st64(win + rd + len - 16, B0);
-          k2_st64(win + rd + len - 8, B1);
-        } else if (len >= 9) {
-          k2_st64(win + rd, A0);
-          k2_st64(win + rd + len - 8, B1);
-        } else if (len >= 4) {
-          k2_st32(win + rd, (u32)A0);
-          k2_st32(win + rd + len - 4, (u32)(A0 >> ((len - 4) * 8)));
-        } else {
-          k2_st16(win + rd, (u32)A0);
-          win[rd + 2] = (u8)(A0 >> 16);
-        }
-      }
-      // the rest of them (long, or at the ring's seam): one at a time, all lanes
-      u64 rest = (farm | symm) & ~tbz_ballot(fw);
-      while (rest) {
-        const u32 i = (u32)tbz_ffs64(rest) - 1;
-        rest &= rest - 1;
-        const u32 di = tbz_readlane(dofs, i);
-        k2_copy_coop<W>(S, rpos, gpos, (i64)gpos + di, tbz_readlane(rd, i), tbz_readlane(dist, i), tbz_readlane(len, i));
-      }
-      pend &= ~(farm | symm);
-      tbz_sync();
-    }
-    if (STAGE == K2_FAR) return;
-    // ---- sources that straddle the group's first octet wait their turn like any other (their part inside the group
-    // must be final), then take the octet-by-octet path
-    const u64 oddq = oddm & pend;
-    // octet-addressed wide LDS accesses: a disjoint match is one or two reads and two (overlapping)
-    // writes that cover exactly [rd, rd + len)
-    const bool fastable = len <= K2_SHORT && dist >= len && rs + 32 <= RW && rd + 32 <= RW;
-    while (pend) {
-      const u32 first = (u32)tbz_ffs64(pend) - 1;
-      if ((oddq >> first) & 1) {  // the first unresolved match is an odd one: everything before it is final
-        k2_copy_coop<W>(S, rpos, gpos, (i64)gpos + tbz_readlane(dofs, first), tbz_readlane(rd, first), tbz_readlane(dist, first),
-                        tbz_readlane(len, first));
-        pend &= pend - 1;
-        tbz_sync();
-        continue;
-      }
-      const i32 hwm = (i32)tbz_readlane(dofs, first);
-      const bool ready = (pend & lane_bit) && need <= hwm && !((oddq >> lane) & 1);
-      const u64 rdy = tbz_ballot(ready);
-      u64 longs = rdy & longm;
-      if (ready && fastable) {
-        if (len >= 17) {
-          const u64 a0 = k2_ld64(win + rs), a1 = k2_ld64(win + rs + 8);
-          const u64 b0 = k2_ld64(win + rs + len - 16), b1 = k2_ld64(win + rs + len - 8);
-          k2_st64(win + rd, a0);
-          k2_st64(win + rd + 8, a1);
-          k2_st64(win + rd + len - 16, b0);
-          k2_st64(win + rd + len - 8, b1);
-        } else if (len >= 9) {
-          const u64 a = k2_ld64(win + rs), b = k2_ld64(win + rs + len - 8);
-          k2_st64(win + rd, a);
-          k2_st64(win + rd + len - 8, b);
-        } else if (len >= 4) {
-          const u64 a = k2_ld64(win + rs);
-          k2_st32(win + rd, (u32)a);
-          k2_st32(win + rd + len - 4, (u32)(a >> ((len - 4) * 8)));
-        } else {
-          const u32 a = k2_ld32(win + rs);
-          k2_st16(win + rd, a);
-          win[rd + 2] = (u8)(a >> 16);
-        }
-      } else if (ready && len <= K2_SHORT) {
-        // overlapping (the match repeats its dist-octet pattern, all of it final already) or at the ring's seam
-        u32 jj = 0;
-        for (u32 j = 0; j < len; j++) {
-          win[ring<W>(rd + j)] = win[ring<W>(rs + jj)];
-          jj = jj + 1 == dist ? 0 : jj + 1;
-        }
-      }
-      while (longs) {
-        const u32 i = (u32)tbz_ffs64(longs) - 1;
-        longs &= longs - 1;
-        k2_copy_coop<W>(S, rpos, gpos, (i64)gpos + tbz_readlane(dofs, i), tbz_readlane(rd, i), tbz_readlane(dist, i), tbz_readlane(len, i));
-      }
-      pend &= ~rdy;
-      tbz_sync();
-    }
-    return;
-  }
-  // ---- LINEAR
-  const bool fastable = len <= K2_SHORT && dist >= len;
 #ifdef TBZ_WAVE_TRACE
   u32 tr_rounds = 0;
   const u32 tr_matches = (u32)tbz_popc64(pend);
@@ -3890,55 +3860,71 @@ TBZ_DEV void k2_resolve(const K2Src& S, u64 pend, u32 rpos, u64 gpos, u32 dofs, 
     tr_rounds += 1;
 #endif
     const u32 first = (u32)tbz_ffs64(pend) - 1;
+    if ((oddq >> first) & 1) {  // the first unresolved match is an odd one: everything before it is final
+      k2_copy_coop<W>(S, rpos, gpos, (i64)gpos + tbz_readlane(dofs, first), tbz_readlane(rd, first), tbz_readlane(dist, first),
+                      tbz_readlane(len, first));
+      pend &= pend - 1;
+      tbz_sync();
+      continue;
+    }
     const i32 hwm = (i32)tbz_readlane(dofs, first);
-    const bool ready = (pend & lane_bit) && need <= hwm;
+    const bool ready = (pend & lane_bit) && need <= hwm && !((oddq >> lane) & 1);
     const u64 rdy = tbz_ballot(ready);
     u64 longs = rdy & longm;
     if (ready && fastable) {
-      if (len >= 17) {
-        // (four 8-octet accesses each way: a 16-octet struct copy took a round trip through scratch memory here)
-        const u64 a0 = k2_ld64(win + rs), a1 = k2_ld64(win + rs + 8);
-        const u64 b0 = k2_ld64(win + rs + len - 16), b1 = k2_ld64(win + rs + len - 8);
-        k2_st64(win + rd, a0);
-        k2_st64(win + rd + 8, a1);
-        k2_st64(win + rd + len - 16, b0);
-        k2_st64(win + rd + len - 8, b1);
-      } else if (len >= 9) {
-        const u64 a = k2_ld64(win + rs), b = k2_ld64(win + rs + len - 8);
-        k2_st64(win + rd, a);
-        k2_st64(win + rd + len - 8, b);
-      } else if (len >= 4) {
-        const u64 a = k2_ld64(win + rs);
-        k2_st32(win + rd, (u32)a);
-        k2_st32(win + rd + len - 4, (u32)(a >> ((len - 4) * 8)));
-      } else {
-        const u32 a = k2_ld32(win + rs);
-        k2_st16(win + rd, a);
-        win[rd + 2] = (u8)(a >> 16);
-      }
+      k2_short_copy(win, rs, rd, len);
     } else if (ready && len <= K2_SHORT) {
-      // overlapping (the match repeats its dist-octet pattern, all of it final already)
-      u32 jj = 0;
-      for (u32 j = 0; j < len; j++) {
-        win[rd + j] = win[rs + jj];
-        jj = jj + 1 == dist ? 0 : jj + 1;
-      }
+      k2_short_octets<W>(win, rs, rd, len, dist);
     }
     while (longs) {
       const u32 i = (u32)tbz_ffs64(longs) - 1;
       longs &= longs - 1;
-      k2_copy_coop<W>(S, rpos, gpos, 0, tbz_readlane(rd, i), tbz_readlane(dist, i), tbz_readlane(len, i));
+      k2_copy_coop<W>(S, rpos, gpos, LINEAR ? 0 : (i64)gpos + tbz_readlane(dofs, i), tbz_readlane(rd, i), tbz_readlane(dist, i),
+                      tbz_readlane(len, i));
     }
     pend &= ~rdy;
     tbz_sync();
   }
 #ifdef TBZ_WAVE_TRACE
-  if (lane == 0 && tr_matches) {
+  if (LINEAR && lane == 0 && tr_matches) {
     atomicAdd(&tbz_dbg_cnt[0], 1u);          // batches with matches
     atomicAdd(&tbz_dbg_cnt[1], tr_rounds);   // rounds
     atomicAdd(&tbz_dbg_cnt[2], tr_matches);  // matches
   }
 #endif
+}
+
+// Multi-round resolution of one batch's matches (at most one per lane).  `pend` = lanes holding an unresolved match;
+// dofs = octet offset of the match inside the batch, whose first octet (group-relative offset gpos) sits at window index
+// rpos.  RING: k2_far_round first, then k2_rounds over what it left.
+// STAGE (ring kernels on three waves, tbz_k2_lz77_ring3): K2_FAR = that first round only, K2_NEAR = everything after it
+// (the far round was another wave's, one batch earlier: its memory round trip is off the resolving wave's path).
+constexpr u32 K2_ALL = 0, K2_FAR = 1, K2_NEAR = 2;
+template <class W, u32 STAGE = K2_ALL>
+TBZ_DEV void k2_resolve(const K2Src& S, u64 pend, u32 rpos, u64 gpos, u32 dofs, u32 len, u32 dist) {
+  static_assert(STAGE == K2_ALL || !W::LINEAR, "stages are the ring kernels'");
+  constexpr bool LINEAR = W::LINEAR;
+  constexpr u32 RW = LINEAR ? 1u : W::RW;
+  // this lane's match in window terms, worked out once for the parts below.  mine: the lane holds an unresolved match;
+  // rd / rs: window index of its first octet / of its source's (sources inside the window); s: group-relative offset of
+  // the source; need: the part of the source the match does not write itself ends at dofs - dist + min(len, dist);
+  // fastable: a short disjoint match away from the ring's seam takes the wide accesses
+  const bool mine = (pend & (1ull << tbz_lane())) != 0;
+  const i32 need = (i32)dofs - (i32)dist + (i32)(len < dist ? len : dist);
+  const u32 rd = ring<W>(rpos + dofs);
+  const u32 rs = LINEAR ? (rd >= dist ? rd - dist : 0) : (rd >= dist % RW ? rd - dist % RW : rd + RW - dist % RW);
+  const u64 longm = tbz_ballot(len > K2_SHORT);
+  const bool fastable = len <= K2_SHORT && dist >= len && (LINEAR || (rs + 32 <= RW && rd + 32 <= RW));
+  const i64 s = (i64)gpos + dofs - (i64)dist;
+  tbz_sync();
+  u64 oddq = 0;
+  if (!W::LINEAR) {
+    u64 oddm;
+    pend &= ~k2_far_round<W, STAGE != K2_NEAR>(S, pend, rpos, gpos, dofs, len, dist, mine, rd, s, oddm);
+    if (STAGE == K2_FAR) return;
+    oddq = oddm & pend;
+  }
+  k2_rounds<W>(S, pend, oddq, rpos, gpos, dofs, len, dist, rd, rs, need, fastable, longm);
 }
 
 
