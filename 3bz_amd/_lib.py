@@ -38,7 +38,7 @@ class Timings(C.Structure):
                 ("find_ms", C.c_float), ("resolve_ms", C.c_float), ("k1_gang", C.c_uint32), ("k2_kinds", C.c_uint32),
                 ("n_candidates", C.c_uint64), ("n_hgroups", C.c_uint64), ("scratch_bytes", C.c_uint64),
                 ("h2d_copies", C.c_uint32), ("passes", C.c_uint32),
-                ("h2d_ms", C.c_float), ("host_decode_ms", C.c_float), ("d2h_ms", C.c_float), ("reserved4", C.c_uint32)]
+                ("h2d_ms", C.c_float), ("host_decode_ms", C.c_float), ("d2h_ms", C.c_float), ("rec_count_us", C.c_uint32)]
 
 
 assert C.sizeof(Result) == 64
@@ -56,6 +56,8 @@ SYMBOLS = [
     "tbz_inflate_sharded_plan", "tbz_inflate_sharded_verdict", "tbz_inflate_sharded_multi",
     "tbz_index_build", "tbz_index_build_device", "tbz_index_destroy", "tbz_index_info", "tbz_index_points",
     "tbz_index_export", "tbz_index_import", "tbz_inflate_ranges", "tbz_inflate_ranges_device",
+    "tbz_index_build_records", "tbz_index_build_records_device", "tbz_index_records_info", "tbz_inflate_records",
+    "tbz_inflate_records_device",
 ]
 
 
@@ -131,6 +133,11 @@ def load(path=None):
     L.tbz_index_import.argtypes = [vp, vp, sz, C.POINTER(vp)]
     L.tbz_inflate_ranges_device.argtypes = [vp, vp, vp, sz, sz, u64p, u64p, vp, u64p, C.POINTER(Result)]
     L.tbz_inflate_ranges.argtypes = [vp, vp, vp, sz, sz, u64p, u64p, C.POINTER(vp), C.POINTER(Result)]
+    L.tbz_index_build_records_device.argtypes = [vp, C.c_int, vp, sz, sz, C.c_int, C.POINTER(vp), C.POINTER(Result)]
+    L.tbz_index_build_records.argtypes = [vp, C.c_int, vp, sz, sz, C.c_int, C.POINTER(vp), C.POINTER(Result)]
+    L.tbz_index_records_info.argtypes = [vp, C.POINTER(C.c_int), szp]
+    L.tbz_inflate_records_device.argtypes = [vp, vp, vp, sz, sz, u64p, u64p, vp, u64p, u64p, C.POINTER(Result)]
+    L.tbz_inflate_records.argtypes = [vp, vp, vp, sz, sz, u64p, u64p, ALLOC_FN, vp, C.POINTER(Result)]
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the ABI is incomplete
     return L

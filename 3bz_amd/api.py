@@ -323,6 +323,57 @@ class Engine:
                                                        a(out_offs), res))
         return list(res)[:n]
 
+    # ---- records: read records i..j of a stream by number (one delimiter octet ends a record)
+    def index_build_records(self, data, fmt, delim, spacing=0, start=0, end=None):
+        """tbz_index_build_records over host octets: as index_build, and the index knows the records `delim` (an int,
+        0..255) cuts the output into"""
+        end = len(data) if end is None else end
+        res, p = _lib.Result(), C.c_void_p()
+        base = _addr(data)
+        self._check(self.lib.tbz_index_build_records(self._ctx, fmt, (base or 0) + start if base else None, end - start,
+                                                     spacing, delim, C.byref(p), C.byref(res)))
+        return (Index(self, p) if p.value else None), res
+
+    def index_build_records_device(self, d_in, in_len, fmt, delim, spacing=0):
+        """the same with the stream in HBM (a raw device pointer)"""
+        res, p = _lib.Result(), C.c_void_p()
+        self._check(self.lib.tbz_index_build_records_device(self._ctx, fmt, d_in, in_len, spacing, delim, C.byref(p),
+                                                            C.byref(res)))
+        return (Index(self, p) if p.value else None), res
+
+    def inflate_records(self, index, data, firsts, counts, start=0, end=None):
+        """tbz_inflate_records: records firsts[i] .. firsts[i] + counts[i] - 1 for every i: (results, list with a bytearray
+        per run — empty for a run of no octets, None for a run whose span failed)"""
+        end = len(data) if end is None else end
+        n = len(firsts)
+        a = self.u64_array
+        res = (_lib.Result * max(1, n))()
+        bufs = []
+
+        def alloc(_user, k):
+            bufs.append(bytearray(k))
+            return C.addressof((C.c_char * k).from_buffer(bufs[-1])) if k else 0
+
+        cb = _lib.ALLOC_FN(alloc)
+        base = _addr(data)
+        self._check(self.lib.tbz_inflate_records(self._ctx, index._ix, (base or 0) + start if base else None, end - start, n,
+                                                 a(firsts), a(counts), cb, None, res))
+        out, it = [], iter(bufs)
+        for r in res[:n]:
+            out.append(None if r.status < 0 else next(it) if r.out_len else bytearray())
+        return list(res)[:n], out
+
+    def inflate_records_device(self, index, d_in, in_len, firsts, counts, d_out, out_offs, out_caps):
+        """tbz_inflate_records_device: the stream and the destination in HBM; run i goes to d_out + out_offs[i], at most
+        out_caps[i] octets of it.  d_out may be None when every capacity is 0: the results then tell where each run
+        lies in the stream's output (boundary_out) and how long it is (out_total)."""
+        n = len(firsts)
+        a = self.u64_array
+        res = (_lib.Result * max(1, n))()
+        self._check(self.lib.tbz_inflate_records_device(self._ctx, index._ix, d_in, in_len, n, a(firsts), a(counts), d_out,
+                                                        a(out_offs), a(out_caps), res))
+        return list(res)[:n]
+
     def trim(self):
         """release the context's device scratch (it only grows otherwise)"""
         self._check(self.lib.tbz_ctx_trim(self._ctx))
@@ -363,6 +414,12 @@ class Index:
         self._eng._check(self._eng.lib.tbz_index_info(self._ix, C.byref(f), *[C.byref(x) for x in v]))
         return {"format": f.value, "in_len": v[0].value, "out_total": v[1].value, "n_points": v[2].value,
                 "max_interval": v[3].value}
+
+    def records_info(self):
+        """dict: delim, n_records (EngineError TBZ_E_ARG for an index built without records)"""
+        d, n = C.c_int(), C.c_size_t()
+        self._eng._check(self._eng.lib.tbz_index_records_info(self._ix, C.byref(d), C.byref(n)))
+        return {"delim": d.value, "n_records": n.value}
 
     def points(self):
         """list of (in_bit, out_off)"""
@@ -802,13 +859,25 @@ def decompress_gzip_members(compressed, start=0, end=None, engine=None):
 # Random access.  The reference's :start / :end select INPUT octets (api.lisp:23-29) and a stream is decoded from its
 # first block; an index (include/tbz_amd.h, tbz_index_*) lets a caller ask for OUTPUT octets instead.
 # ------------------------------------------------------------------------------------------------
-def build_index(compressed, format="zlib", spacing=0, engine=None):
+def _delim_octet(delim):
+    if isinstance(delim, (bytes, bytearray)):
+        if len(delim) != 1:
+            raise ValueError("a delimiter is one octet")
+        return delim[0]
+    return int(delim)
+
+
+def build_index(compressed, format="zlib", spacing=0, engine=None, delim=None):
     """decode the stream once and keep its proven block starts: an Index.  A stream that decompress_vector would not
-    accept raises what decompress_vector raises."""
+    accept raises what decompress_vector raises.  delim (an int 0..255 or one octet, e.g. b"\n"): the index also knows
+    the records that octet ends, for decompress_records."""
     fmt = FORMATS[format] if isinstance(format, str) else format
     name = format if isinstance(format, str) else {0: "deflate", 1: "zlib", 2: "gzip"}[fmt]
     eng = engine or default_engine()
-    ix, res = eng.index_build(compressed, fmt, spacing)
+    if delim is None:
+        ix, res = eng.index_build(compressed, fmt, spacing)
+    else:
+        ix, res = eng.index_build_records(compressed, fmt, _delim_octet(delim), spacing)
     if res.status < 0:
         raise ThreeBzError(res.status, eng.strerror(res.status))
     if ix is None:
@@ -823,6 +892,18 @@ def decompress_ranges(compressed, index, ranges, engine=None):
     total = index.info()["out_total"]
     outs = [bytearray(max(0, min(ln, total - off))) for off, ln in ranges]
     res = eng.inflate_ranges(index, compressed, [r[0] for r in ranges], [r[1] for r in ranges], outs)
+    for r in res:
+        if r.status < 0:
+            raise ThreeBzError(r.status, eng.strerror(r.status))
+    return outs
+
+
+def decompress_records(compressed, index, runs, engine=None):
+    """records first .. first + count - 1 of the stream's output for every (first, count) of `runs`: a list of bytearrays,
+    each the run's records with their delimiters (clipped at the last record like read(2)).  The index comes from
+    build_index(..., delim=...).  A run whose part of the stream is damaged raises ThreeBzError."""
+    eng = engine or index._eng
+    res, outs = eng.inflate_records(index, compressed, [r[0] for r in runs], [r[1] for r in runs])
     for r in res:
         if r.status < 0:
             raise ThreeBzError(r.status, eng.strerror(r.status))

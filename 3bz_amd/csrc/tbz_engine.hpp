@@ -59,7 +59,7 @@ struct DevBuf {
   X(d_markers2) X(d_kb_fm2) X(d_mark) X(d_hg) X(d_k6s) X(d_bigs) X(d_recs) X(d_kc_tf) \
   X(d_kc_slots) X(d_kc_ends) X(d_kc_link) X(d_kc_fm2) X(d_markers3) X(d_kb_keep) X(d_kb_kcounts) X(d_gz_cands) \
   X(d_gz_count) X(d_gz_tmp) X(d_wide_res) X(d_cold) X(d_cold2) X(d_small_rec) \
-  X(d_bit_off) X(d_ix_span) X(d_ix_recs)
+  X(d_bit_off) X(d_ix_span) X(d_ix_recs) X(d_rec_pieces) X(d_rec_queries) X(d_rec_out)
 
 namespace tbz {
 // A few host threads that copy between a caller's (pageable) buffer and the pinned staging buffers: one thread moves
@@ -3933,12 +3933,18 @@ struct tbz_index {
   std::vector<uint32_t> crc;       // crc32 (init 0) of the output octets [out_off[k], out_off[k + 1]) (the last: to out_total)
   void* d_win = nullptr;
   uint64_t win_bytes = 0;
+  // records (tbz_index_build_records*): -1 for an index without them
+  int delim = -1;
+  uint64_t n_delims = 0, n_records = 0;
+  std::vector<uint64_t> rec_before;  // delimiter octets in output [0, out_off[k])
   uint64_t interval_end(size_t k) const { return k + 1 < out_off.size() ? out_off[k + 1] : out_total; }
+  uint64_t delims_end(size_t k) const { return k + 1 < rec_before.size() ? rec_before[k + 1] : n_delims; }
 };
 
 namespace tbz {
 constexpr uint32_t IX_MAGIC = 0x585a4254u;  // "TBZX"
-constexpr uint32_t IX_VERSION = 1;
+constexpr uint32_t IX_VERSION = 1, IX_VERSION_RECORDS = 2;
+constexpr size_t IX_REC_HEAD = 24;          // version 2: the record fields' scalars
 constexpr size_t IX_HEAD = 56;              // the blob's scalar fields (see tbz_index_export)
 constexpr uint64_t IX_MIN_IN_BITS = 512;    // successive points are at least 64 input octets apart
 constexpr uint64_t IX_WIN = 32768;
@@ -4006,23 +4012,13 @@ struct IxPlan {
   std::vector<int64_t> span_of;      // per range: its span, -1 for a range of no octets
   std::vector<uint64_t> out_len;     // per range, clipped at the end of the stream
 };
-static void ix_plan(const tbz_index* ix, size_t n, const uint64_t* offs, const uint64_t* lens, IxPlan& P) {
+struct IxWant { size_t p, q, i; };  // request i needs the intervals [p, q)
+// the spans that cover `v` (ranges and record runs alike)
+static void ix_plan_spans(const tbz_index* ix, size_t n, std::vector<IxWant>& v, IxPlan& P) {
   const size_t np = ix->out_off.size();
-  struct PQ { size_t p, q, i; };
-  std::vector<PQ> v;
   P.span_of.assign(n, -1);
-  P.out_len.assign(n, 0);
-  for (size_t i = 0; i < n; i++) {
-    const uint64_t off = offs[i];
-    const uint64_t ol = off >= ix->out_total ? 0 : std::min<uint64_t>(lens[i], ix->out_total - off);
-    P.out_len[i] = ol;
-    if (!ol) continue;
-    const size_t p = (size_t)(std::upper_bound(ix->out_off.begin(), ix->out_off.end(), off) - ix->out_off.begin()) - 1;
-    const size_t q = (size_t)(std::lower_bound(ix->out_off.begin(), ix->out_off.end(), off + ol) - ix->out_off.begin());
-    v.push_back(PQ{p, q, i});
-  }
-  std::sort(v.begin(), v.end(), [](const PQ& a, const PQ& b) { return a.p != b.p ? a.p < b.p : a.i < b.i; });
-  for (const PQ& e : v) {
+  std::sort(v.begin(), v.end(), [](const IxWant& a, const IxWant& b) { return a.p != b.p ? a.p < b.p : a.i < b.i; });
+  for (const IxWant& e : v) {
     // overlapping OR touching spans are merged: what stays apart is apart by a whole interval, i.e. by at least 64 input
     // octets — the token pool is addressed by input position, so two streams of a call may not share an input octet
     if (P.spans.empty() || e.p > P.spans.back().q) {
@@ -4044,11 +4040,61 @@ static void ix_plan(const tbz_index* ix, size_t n, const uint64_t* offs, const u
     s.ok = false;
   }
 }
+static void ix_plan(const tbz_index* ix, size_t n, const uint64_t* offs, const uint64_t* lens, IxPlan& P) {
+  std::vector<IxWant> v;
+  P.out_len.assign(n, 0);
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t off = offs[i];
+    const uint64_t ol = off >= ix->out_total ? 0 : std::min<uint64_t>(lens[i], ix->out_total - off);
+    P.out_len[i] = ol;
+    if (!ol) continue;
+    const size_t p = (size_t)(std::upper_bound(ix->out_off.begin(), ix->out_off.end(), off) - ix->out_off.begin()) - 1;
+    const size_t q = (size_t)(std::lower_bound(ix->out_off.begin(), ix->out_off.end(), off + ol) - ix->out_off.begin());
+    v.push_back(IxWant{p, q, i});
+  }
+  ix_plan_spans(ix, n, v, P);
+}
+// A run of records (first, count), clipped at n_records.  The interval that holds delimiter octet d is the last one with
+// rec_before[k] <= d: the run's span goes from the interval of the delimiter in front of its first record (the record's
+// first octet is the one behind it) to the interval of the delimiter that ends its last record, or to the end of the stream.
+struct RecRun {
+  bool empty = true;
+  uint64_t d_first = 0, d_last = 0;  // ordinals of those two delimiters
+  bool from_start = false, to_end = false;  // record 0: no delimiter in front; the final record without one: none behind
+  size_t k_first = 0, k_last = 0;    // their intervals
+  uint64_t start = 0, len = 0;       // the run's octets in the stream's output, known once its span is decoded
+};
+static void rec_plan(const tbz_index* ix, size_t n, const uint64_t* firsts, const uint64_t* counts, std::vector<RecRun>& runs,
+                     IxPlan& P) {
+  const size_t np = ix->out_off.size();
+  auto interval_of = [&](uint64_t d) {
+    return (size_t)(std::upper_bound(ix->rec_before.begin(), ix->rec_before.end(), d) - ix->rec_before.begin()) - 1;
+  };
+  std::vector<IxWant> v;
+  runs.assign(n, RecRun{});
+  P.out_len.assign(n, 0);
+  for (size_t i = 0; i < n; i++) {
+    if (firsts[i] >= ix->n_records || !counts[i]) continue;
+    RecRun& R = runs[i];
+    R.empty = false;
+    const uint64_t last = firsts[i] + std::min<uint64_t>(counts[i], ix->n_records - firsts[i]) - 1;
+    R.from_start = firsts[i] == 0;
+    R.to_end = last >= ix->n_delims;
+    if (!R.from_start) R.k_first = interval_of(R.d_first = firsts[i] - 1);
+    if (!R.to_end) R.k_last = interval_of(R.d_last = last);
+    v.push_back(IxWant{R.from_start ? 0 : R.k_first, R.to_end ? np : R.k_last + 1, i});
+  }
+  ix_plan_spans(ix, n, v, P);
+}
 
 // decode the plan's spans (in consecutive sub-batches when their scratch would exceed the pool cap), check every
-// interval, deliver the ranges of the spans that are sound to d_out + out_offs[i], fill the results
-static int ix_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P, size_t n, const uint64_t* offs, void* d_out,
-                  const uint64_t* out_offs, tbz_result* results) {
+// interval; then `deliver` names, for the spans [a, b) of the sub-batch, what goes from the span scratch to d_out (ranges:
+// the requested octets of the spans that are sound; record runs: after counting and locating their delimiters there);
+// fill what every request of a span reports (status, boundary_out, segments, in_consumed, flags)
+using IxDeliver = std::function<int(size_t a, size_t b, std::vector<IxRec>& recs)>;
+// (d_out is read after `deliver` has run: the host variant of the record calls sizes its staging buffer there)
+static int ix_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P, size_t n, void* const* d_out,
+                  tbz_result* results, const IxDeliver& deliver) {
   const size_t np = ix->out_off.size(), ns = P.spans.size();
   int r;
   tbz_timings acc{};
@@ -4136,13 +4182,8 @@ static int ix_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P
     }
     // ---- only now the requested octets go to the caller
     recs.clear();
-    for (size_t i = 0; i < n; i++) {
-      const int64_t si = P.span_of[i];
-      if (si < (int64_t)a || si >= (int64_t)b || !P.spans[si].ok) continue;
-      const IxSpan& s = P.spans[si];
-      recs.push_back(IxRec{s.out_base + (offs[i] - ix->out_off[s.p]), out_offs[i], P.out_len[i]});
-    }
-    if ((r = ix_copy(ctx, ctx->d_ix_span.p, d_out, recs))) return r;
+    if ((r = deliver(a, b, recs))) return r;
+    if ((r = ix_copy(ctx, ctx->d_ix_span.p, *d_out, recs))) return r;
     TBZ_HIP(hipStreamSynchronize(ctx->stream));  // (the next sub-batch reuses the scratch and the record list)
     a = b;
   }
@@ -4156,7 +4197,6 @@ static int ix_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P
     tbz_result& R = results[i];
     memset(&R, 0, sizeof R);
     R.status = TBZ_FINISHED;
-    R.out_total = ix->out_total;
     const int64_t si = P.span_of[i];
     if (si < 0) continue;
     const IxSpan& s = P.spans[si];
@@ -4170,6 +4210,168 @@ static int ix_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P
   return 0;
 }
 
+static int ix_run_ranges(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P, size_t n, const uint64_t* offs,
+                         void* d_out, const uint64_t* out_offs, tbz_result* results) {
+  int r = ix_run(ctx, ix, d_in, P, n, &d_out, results, [&](size_t a, size_t b, std::vector<IxRec>& recs) {
+    for (size_t i = 0; i < n; i++) {
+      const int64_t si = P.span_of[i];
+      if (si < (int64_t)a || si >= (int64_t)b || !P.spans[si].ok) continue;
+      const IxSpan& s = P.spans[si];
+      recs.push_back(IxRec{s.out_base + (offs[i] - ix->out_off[s.p]), out_offs[i], P.out_len[i]});
+    }
+    return 0;
+  });
+  if (r) return r;
+  for (size_t i = 0; i < n; i++) results[i].out_total = ix->out_total;
+  return 0;
+}
+
+// ---- records: the delimiter octets of intervals, counted and located on the device
+// the pieces (tbz_rec_count: a workgroup each) of `len` octets at `src`; their counts go to slots first .. of the count array
+static void rec_cut(std::vector<RecPiece>& pieces, uint64_t src, uint64_t len) {
+  for (uint64_t o = 0; o < len; o += IX_PIECE)
+    pieces.push_back(RecPiece{src + o, (u32)std::min<uint64_t>(IX_PIECE, len - o), (u32)pieces.size()});
+}
+// count the pieces, answer the queries (their cnt0 are slots of these pieces), and bring counts and positions back in
+// one copy.  The count array is u32 per piece, the positions u64 per query behind it.
+static int rec_scan(tbz_ctx* ctx, const void* src, int delim, const std::vector<RecPiece>& pieces, const std::vector<RecQuery>& queries,
+                    std::vector<uint32_t>& counts, std::vector<uint64_t>& pos) {
+  counts.assign(pieces.size(), 0);
+  pos.assign(queries.size(), REC_NONE);
+  if (pieces.empty()) return 0;
+  if (pieces.size() > 0xffffffffull) return TBZ_E_UNSUPPORTED;  // (2^48 octets in one call)
+  int r;
+  const size_t pos_at = (pieces.size() * 4 + 15) & ~(size_t)15, bytes = pos_at + queries.size() * 8;
+  if ((r = upload(ctx, ctx->d_rec_pieces, pieces))) return r;
+  if ((r = upload(ctx, ctx->d_rec_queries, queries))) return r;
+  if ((r = ensure(ctx, ctx->d_rec_out, bytes + 16))) return r;
+  const u32 delim4 = (u32)delim * 0x01010101u;
+  u32* d_counts = (u32*)ctx->d_rec_out.p;
+  constexpr size_t MAX_GRID = 1u << 23;  // (x 256 lanes: within a launch's 2^32 threads)
+  for (size_t a = 0; a < pieces.size(); a += MAX_GRID) {
+    const size_t cnt = std::min(MAX_GRID, pieces.size() - a);
+    RecCountParams p{(const u8*)src, (const RecPiece*)ctx->d_rec_pieces.p + a, d_counts, (u32)cnt, delim4};
+    TBZ_LAUNCH_WG(tbz_rec_count, cnt, IX_THREADS, ctx->stream, p);
+  }
+  for (size_t a = 0; a < queries.size(); a += MAX_GRID) {
+    const size_t cnt = std::min(MAX_GRID, queries.size() - a);
+    RecLocateParams p{(const u8*)src, (const RecQuery*)ctx->d_rec_queries.p + a, d_counts,
+                      (u64*)((u8*)ctx->d_rec_out.p + pos_at) + a, (u32)cnt, delim4};
+    TBZ_LAUNCH_WG(tbz_rec_locate, cnt, IX_THREADS, ctx->stream, p);
+  }
+  TBZ_HIP(hipGetLastError());
+  std::vector<uint8_t> back(bytes);
+  if ((r = read_back(ctx, back.data(), ctx->d_rec_out.p, bytes))) return r;
+  memcpy(counts.data(), back.data(), pieces.size() * 4);
+  if (!queries.empty()) memcpy(pos.data(), back.data() + pos_at, queries.size() * 8);
+  return 0;
+}
+
+// the record runs of a call over ix_run: per sub-batch, every interval of the sound spans is counted and compared with
+// the index, the two delimiters that bound each run are located, and min(run, capacity) octets are named for delivery.
+// out_offs NULL (the host variant): the destinations are handed out here, one after another in d_out_stage, which keeps
+// what earlier sub-batches put there when it has to grow.
+struct RecCall {
+  std::vector<RecRun> runs;
+  std::vector<uint64_t> place;  // host variant: where run i lies in d_out_stage
+  uint64_t placed = 0;
+};
+static int rec_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P, RecCall& C, size_t n, void* const* d_out,
+                   const uint64_t* out_offs, const uint64_t* out_caps, tbz_result* results) {
+  const bool host = !out_offs;
+  if (host) C.place.assign(n, 0);
+  int r = ix_run(ctx, ix, d_in, P, n, d_out, results, [&](size_t a, size_t b, std::vector<IxRec>& recs) -> int {
+    std::vector<RecPiece> pieces;
+    std::vector<RecQuery> queries;
+    struct Iv { size_t span, k; uint32_t cnt0; };
+    std::vector<Iv> ivs;
+    std::vector<std::vector<uint32_t>> first_slot(b - a);  // per span of the sub-batch, per interval: its first piece
+    for (size_t si = a; si < b; si++) {
+      const IxSpan& s = P.spans[si];
+      if (!s.ok) continue;
+      for (size_t k = s.p; k < s.q; k++) {
+        ivs.push_back(Iv{si, k, (uint32_t)pieces.size()});
+        first_slot[si - a].push_back((uint32_t)pieces.size());
+        rec_cut(pieces, s.out_base + (ix->out_off[k] - ix->out_off[s.p]), ix->interval_end(k) - ix->out_off[k]);
+      }
+    }
+    std::vector<size_t> qfirst(n, 0);  // per run of the sub-batch: its first query
+    auto ask = [&](const IxSpan& s, size_t si, size_t k, uint64_t d) {
+      queries.push_back(RecQuery{s.out_base + (ix->out_off[k] - ix->out_off[s.p]), ix->interval_end(k) - ix->out_off[k],
+                                 d - ix->rec_before[k], first_slot[si - a][k - s.p], 0u});
+    };
+    for (size_t i = 0; i < n; i++) {
+      const int64_t si = P.span_of[i];
+      if (si < (int64_t)a || si >= (int64_t)b || !P.spans[si].ok) continue;
+      const RecRun& R = C.runs[i];
+      qfirst[i] = queries.size();
+      if (!R.from_start) ask(P.spans[si], (size_t)si, R.k_first, R.d_first);
+      if (!R.to_end) ask(P.spans[si], (size_t)si, R.k_last, R.d_last);
+    }
+    std::vector<uint32_t> counts;
+    std::vector<uint64_t> pos;
+    int rr;
+    if ((rr = rec_scan(ctx, ctx->d_ix_span.p, ix->delim, pieces, queries, counts, pos))) return rr;
+    // an interval that holds another number of delimiters than the index says is not what the index recorded
+    for (size_t v = 0; v < ivs.size(); v++) {
+      const size_t end = v + 1 < ivs.size() ? ivs[v + 1].cnt0 : pieces.size();
+      uint64_t sum = 0;
+      for (size_t c = ivs[v].cnt0; c < end; c++) sum += counts[c];
+      if (sum != ix->delims_end(ivs[v].k) - ix->rec_before[ivs[v].k]) {
+        P.spans[ivs[v].span].ok = false;
+        P.spans[ivs[v].span].status = TBZ_E_CRC32;
+      }
+    }
+    uint64_t need = C.placed;
+    for (size_t i = 0; i < n; i++) {
+      const int64_t si = P.span_of[i];
+      if (si < (int64_t)a || si >= (int64_t)b || !P.spans[si].ok) continue;
+      RecRun& R = C.runs[i];
+      size_t q = qfirst[i];
+      const uint64_t p0 = R.from_start ? 0 : pos[q++], p1 = R.to_end ? 0 : pos[q];
+      if (p0 == REC_NONE || p1 == REC_NONE) return TBZ_E_INTERNAL;  // (the counts were right: the octets are there)
+      R.start = R.from_start ? 0 : ix->out_off[R.k_first] + p0 + 1;
+      R.len = (R.to_end ? ix->out_total : ix->out_off[R.k_last] + p1 + 1) - R.start;
+      P.out_len[i] = host ? R.len : std::min<uint64_t>(R.len, out_caps[i]);
+      if (host) {
+        C.place[i] = need;
+        need = (need + R.len + 15) & ~15ull;
+      }
+    }
+    if (host && need + 64 > ctx->d_out_stage.cap) {  // grow, keeping what earlier sub-batches delivered
+      DevBuf old = ctx->d_out_stage;
+      ctx->d_out_stage = DevBuf{};
+      if ((rr = ensure(ctx, ctx->d_out_stage, need + 64))) {
+        ctx->d_out_stage = old;
+        return rr;
+      }
+      if (old.p) {
+        if (C.placed) TBZ_HIP(hipMemcpyAsync(ctx->d_out_stage.p, old.p, C.placed, hipMemcpyDeviceToDevice, ctx->stream));
+        TBZ_HIP(hipStreamSynchronize(ctx->stream));
+        TBZ_HIP(hipFree(old.p));
+      }
+    }
+    C.placed = need;
+    for (size_t i = 0; i < n; i++) {
+      const int64_t si = P.span_of[i];
+      if (si < (int64_t)a || si >= (int64_t)b || !P.spans[si].ok || !P.out_len[i]) continue;
+      const IxSpan& s = P.spans[si];
+      recs.push_back(IxRec{s.out_base + (C.runs[i].start - ix->out_off[s.p]), host ? C.place[i] : out_offs[i], P.out_len[i]});
+    }
+    return 0;
+  });
+  if (r) return r;
+  for (size_t i = 0; i < n; i++) {
+    tbz_result& R = results[i];
+    const int64_t si = P.span_of[i];
+    if (si < 0 || !P.spans[si].ok) continue;  // an empty run, or a failed span: no octets
+    R.out_total = C.runs[i].len;
+    R.boundary_out = C.runs[i].start;
+    if (R.out_len < R.out_total) R.status = TBZ_OUTPUT_OVERFLOW;
+  }
+  return 0;
+}
+
 static int ix_check_args(tbz_ctx* ctx, const tbz_index* ix, size_t in_len, size_t n, const uint64_t* offs, const uint64_t* lens,
                          const void* outs, tbz_result* results) {
   if (!ctx || !ix || ix->ctx != ctx || (n && (!offs || !lens || !outs || !results))) return TBZ_E_ARG;
@@ -4179,13 +4381,13 @@ static int ix_check_args(tbz_ctx* ctx, const tbz_index* ix, size_t in_len, size_
 }
 }  // namespace tbz
 
-extern "C" {
-
-int tbz_index_build_device(tbz_ctx* ctx, int format, const void* d_in, size_t in_len, size_t spacing, tbz_index** out_index,
-                           tbz_result* res) {
+// the index of a stream in device memory; delim >= 0: with records (tbz_index_build_records*)
+static int tbz_ix_build_device(tbz_ctx* ctx, int format, const void* d_in, size_t in_len, size_t spacing, int delim,
+                               tbz_index** out_index, tbz_result* res) {
   using namespace tbz;
   if (!ctx || !out_index || !res || format < 0 || format > 2 || (in_len && !d_in)) return TBZ_E_ARG;
   *out_index = nullptr;
+  if (delim > 255) return TBZ_E_ARG;
   TBZ_HIP(hipSetDevice(ctx->device));
   // point 0: the first block's bit (the head item starts at the container header, not at a block)
   uint64_t first_bit = format == TBZ_FORMAT_ZLIB ? 16 : 0;
@@ -4252,22 +4454,82 @@ int tbz_index_build_device(tbz_ctx* ctx, int format, const void* d_in, size_t in
   for (size_t k = 0; k < np; k++)
     if (!cl[k]) ix->crc[k] = 0;
   ctx->tim = tim;
+  if (delim >= 0) {
+    // records: the delimiter octets of every interval, counted over the output where it still lies; one more piece of
+    // one octet tells whether the stream ends in one
+    std::vector<RecPiece> pieces;
+    std::vector<uint32_t> first(np + 1), counts;
+    std::vector<uint64_t> none;
+    for (size_t k = 0; k < np; k++) {
+      first[k] = (uint32_t)pieces.size();
+      rec_cut(pieces, co[k], cl[k]);
+    }
+    first[np] = (uint32_t)pieces.size();
+    if (total) rec_cut(pieces, total - 1, 1);
+    if ((r = record(ctx, 10))) return fail(r);
+    if ((r = rec_scan(ctx, ctx->d_out_stage.p, delim, pieces, {}, counts, none))) return fail(r);
+    if ((r = record(ctx, 11))) return fail(r);
+    if (hipEventSynchronize(ctx->ev[11]) == hipSuccess) ctx->tim.rec_count_us = (uint32_t)(elapsed(ctx, 10, 11) * 1000.0f + 0.5f);
+    ix->delim = delim;
+    ix->rec_before.resize(np);
+    uint64_t sum = 0;
+    for (size_t k = 0; k < np; k++) {
+      ix->rec_before[k] = sum;
+      for (uint32_t c = first[k]; c < first[k + 1]; c++) sum += counts[c];
+    }
+    ix->n_delims = sum;
+    ix->n_records = sum + (total && !counts[first[np]] ? 1 : 0);
+  }
   *out_index = ix;
   return 0;
 }
 
-int tbz_index_build(tbz_ctx* ctx, int format, const uint8_t* in, size_t in_len, size_t spacing, tbz_index** out_index,
-                    tbz_result* res) {
+extern "C" {
+
+int tbz_index_build_device(tbz_ctx* ctx, int format, const void* d_in, size_t in_len, size_t spacing, tbz_index** out_index,
+                           tbz_result* res) {
+  return tbz_ix_build_device(ctx, format, d_in, in_len, spacing, -1, out_index, res);
+}
+
+int tbz_index_build_records_device(tbz_ctx* ctx, int format, const void* d_in, size_t in_len, size_t spacing, int delim,
+                                   tbz_index** out_index, tbz_result* res) {
+  if (out_index) *out_index = nullptr;
+  if (delim < 0 || delim > 255) return TBZ_E_ARG;
+  return tbz_ix_build_device(ctx, format, d_in, in_len, spacing, delim, out_index, res);
+}
+
+static int tbz_ix_build_host(tbz_ctx* ctx, int format, const uint8_t* in, size_t in_len, size_t spacing, int delim,
+                             tbz_index** out_index, tbz_result* res) {
   using namespace tbz;
   if (!ctx || !out_index || !res || (in_len && !in)) return TBZ_E_ARG;
   *out_index = nullptr;
+  if (delim > 255) return TBZ_E_ARG;
   TBZ_HIP(hipSetDevice(ctx->device));
   int r;
   if ((r = ensure(ctx, ctx->d_in_stage, in_len + 64))) return r;
   if ((r = stage_in(ctx, ctx->d_in_stage.p, in, in_len))) return r;
-  r = tbz_index_build_device(ctx, format, ctx->d_in_stage.p, in_len, spacing, out_index, res);
+  r = tbz_ix_build_device(ctx, format, ctx->d_in_stage.p, in_len, spacing, delim, out_index, res);
   ctx->tim.h2d_copies = in_len ? 1u : 0u;
   return r;
+}
+
+int tbz_index_build(tbz_ctx* ctx, int format, const uint8_t* in, size_t in_len, size_t spacing, tbz_index** out_index,
+                    tbz_result* res) {
+  return tbz_ix_build_host(ctx, format, in, in_len, spacing, -1, out_index, res);
+}
+
+int tbz_index_build_records(tbz_ctx* ctx, int format, const uint8_t* in, size_t in_len, size_t spacing, int delim,
+                            tbz_index** out_index, tbz_result* res) {
+  if (out_index) *out_index = nullptr;
+  if (delim < 0 || delim > 255) return TBZ_E_ARG;
+  return tbz_ix_build_host(ctx, format, in, in_len, spacing, delim, out_index, res);
+}
+
+int tbz_index_records_info(const tbz_index* ix, int* delim, size_t* n_records) {
+  if (!ix || ix->delim < 0) return TBZ_E_ARG;
+  if (delim) *delim = ix->delim;
+  if (n_records) *n_records = (size_t)ix->n_records;
+  return 0;
 }
 
 void tbz_index_destroy(tbz_index* ix) {
@@ -4305,7 +4567,9 @@ int tbz_index_points(const tbz_index* ix, size_t max, uint64_t* in_bit, uint64_t
 }
 
 // the blob, little-endian: u32 magic, version, format, check; u64 in_len, out_total, first_block_bit, n_points, window
-// octets; u64 in_bit[n]; u64 out_off[n]; u32 win_len[n]; u32 crc[n]; the windows, one after another; u32 crc32 of all that
+// octets; u64 in_bit[n]; u64 out_off[n]; u32 win_len[n]; u32 crc[n]; the windows, one after another; u32 crc32 of all that.
+// An index with records is version 2: between crc[n] and the windows u32 delim, u32 0, u64 n_delims, u64 n_records,
+// u64 rec_before[n].  An index without them is version 1, octet for octet what it was before there were records.
 int tbz_index_export(const tbz_index* ix, uint8_t* buf, size_t cap, size_t* need) {
   using namespace tbz;
   if (!ix || !need) return TBZ_E_ARG;
@@ -4313,19 +4577,24 @@ int tbz_index_export(const tbz_index* ix, uint8_t* buf, size_t cap, size_t* need
   const size_t np = ix->out_off.size();
   uint64_t wsum = 0;
   for (uint32_t w : ix->win_len) wsum += w;
-  const size_t size = IX_HEAD + np * 24 + (size_t)wsum + 4;
+  const bool rec = ix->delim >= 0;
+  const size_t size = IX_HEAD + np * 24 + (rec ? IX_REC_HEAD + np * 8 : 0) + (size_t)wsum + 4;
   *need = size;
   if (!buf) return 0;
   if (cap < size) return TBZ_E_ARG;
   uint8_t* p = buf;
   auto put32 = [&](uint32_t v) { memcpy(p, &v, 4); p += 4; };
   auto put64 = [&](uint64_t v) { memcpy(p, &v, 8); p += 8; };
-  put32(IX_MAGIC); put32(IX_VERSION); put32((uint32_t)ix->format); put32(ix->check);
+  put32(IX_MAGIC); put32(rec ? IX_VERSION_RECORDS : IX_VERSION); put32((uint32_t)ix->format); put32(ix->check);
   put64(ix->in_len); put64(ix->out_total); put64(ix->first_block_bit); put64(np); put64(wsum);
   for (uint64_t v : ix->in_bit) put64(v);
   for (uint64_t v : ix->out_off) put64(v);
   for (uint32_t v : ix->win_len) put32(v);
   for (uint32_t v : ix->crc) put32(v);
+  if (rec) {
+    put32((uint32_t)ix->delim); put32(0); put64(ix->n_delims); put64(ix->n_records);
+    for (uint64_t v : ix->rec_before) put64(v);
+  }
   if (wsum) {
     TBZ_HIP(hipSetDevice(ctx->device));
     std::vector<uint8_t> w(ix->win_bytes);
@@ -4348,11 +4617,15 @@ int tbz_index_import(tbz_ctx* ctx, const uint8_t* buf, size_t len, tbz_index** o
   const uint8_t* p = buf;
   auto get32 = [&]() { uint32_t v; memcpy(&v, p, 4); p += 4; return v; };
   auto get64 = [&]() { uint64_t v; memcpy(&v, p, 8); p += 8; return v; };
-  if (get32() != IX_MAGIC || get32() != IX_VERSION) return TBZ_E_ARG;
+  if (get32() != IX_MAGIC) return TBZ_E_ARG;
+  const uint32_t version = get32();
+  if (version != IX_VERSION && version != IX_VERSION_RECORDS) return TBZ_E_ARG;
+  const bool rec = version == IX_VERSION_RECORDS;
   const uint32_t format = get32(), check = get32();
   const uint64_t in_len = get64(), out_total = get64(), first_bit = get64(), np = get64(), wsum = get64();
   if (format > 2 || np == 0 || np > (len - IX_HEAD - 4) / 24) return TBZ_E_ARG;
-  if (wsum > len || IX_HEAD + np * 24 + wsum + 4 != len) return TBZ_E_ARG;  // the sizes add up
+  const uint64_t rec_bytes = rec ? IX_REC_HEAD + np * 8 : 0;
+  if (wsum > len || IX_HEAD + np * 24 + rec_bytes + wsum + 4 != len) return TBZ_E_ARG;  // the sizes add up
   uint32_t stored;
   memcpy(&stored, buf + len - 4, 4);
   if (ix_crc32(buf, len - 4) != stored) return TBZ_E_ARG;
@@ -4370,6 +4643,24 @@ int tbz_index_import(tbz_ctx* ctx, const uint8_t* buf, size_t len, tbz_index** o
   for (auto& v : ix->out_off) v = get64();
   for (auto& v : wl) v = get32();
   for (auto& v : ix->crc) v = get32();
+  if (rec) {
+    const uint32_t delim = get32(), pad = get32();
+    ix->n_delims = get64();
+    ix->n_records = get64();
+    ix->rec_before.resize(np);
+    for (auto& v : ix->rec_before) v = get64();
+    if (delim > 255 || pad != 0 || ix->rec_before[0] != 0) return TBZ_E_ARG;
+    ix->delim = (int)delim;
+    // no interval (and not the tail) holds more delimiter octets than octets; one record per delimiter, and one more
+    // for octets behind the last
+    for (size_t k = 0; k < np; k++) {
+      const uint64_t hi = ix->delims_end(k), octets = (k + 1 < np ? ix->out_off[k + 1] : out_total) - ix->out_off[k];
+      if (hi < ix->rec_before[k] || (k + 1 < np && ix->out_off[k + 1] < ix->out_off[k]) || out_total < ix->out_off[k]) return TBZ_E_ARG;
+      if (hi - ix->rec_before[k] > octets) return TBZ_E_ARG;
+    }
+    if (ix->n_records != ix->n_delims && ix->n_records != ix->n_delims + 1) return TBZ_E_ARG;
+    if (ix->n_records != ix->n_delims && out_total == 0) return TBZ_E_ARG;
+  }
   // consistent in itself: point 0 where the first block is, both offsets ascending as the builder spaces them, every
   // point inside the stream, every window exactly the octets in front of its point
   if (ix->out_off[0] != 0 || ix->in_bit[0] != first_bit) return TBZ_E_ARG;
@@ -4418,7 +4709,7 @@ int tbz_inflate_ranges_device(tbz_ctx* ctx, const tbz_index* ix, const void* d_i
   IxPlan P;
   ix_plan(ix, n, offs, lens, P);
   if (!P.spans.empty() && !d_out) return TBZ_E_ARG;
-  return ix_run(ctx, ix, d_in, P, n, offs, d_out, out_offs, results);
+  return ix_run_ranges(ctx, ix, d_in, P, n, offs, d_out, out_offs, results);
 }
 
 int tbz_inflate_ranges(tbz_ctx* ctx, const tbz_index* ix, const uint8_t* in, size_t in_len, size_t n, const uint64_t* offs,
@@ -4448,13 +4739,66 @@ int tbz_inflate_ranges(tbz_ctx* ctx, const tbz_index* ix, const uint8_t* in, siz
     ot = (ot + P.out_len[i] + 15) & ~15ull;
   }
   if ((r = ensure(ctx, ctx->d_out_stage, ot + 64))) return r;
-  if ((r = ix_run(ctx, ix, ctx->d_in_stage.p, P, n, offs, ctx->d_out_stage.p, oo.data(), results))) return r;
+  if ((r = ix_run_ranges(ctx, ix, ctx->d_in_stage.p, P, n, offs, ctx->d_out_stage.p, oo.data(), results))) return r;
   ctx->tim.h2d_copies = pin.empty() ? 0u : 1u;
   std::vector<StagePiece> pout;
   for (size_t i = 0; i < n; i++)
     if (results[i].out_len) {
       if (!outs[i]) return TBZ_E_ARG;
       pout.push_back(StagePiece{outs[i], oo[i], results[i].out_len});
+    }
+  return stage_out(ctx, ctx->d_out_stage.p, pout);
+}
+
+int tbz_inflate_records_device(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, size_t in_len, size_t n, const uint64_t* firsts,
+                               const uint64_t* counts, void* d_out, const uint64_t* out_offs, const uint64_t* out_caps,
+                               tbz_result* results) {
+  using namespace tbz;
+  int r;
+  if (ix && ix->delim < 0) return TBZ_E_ARG;
+  if (n && !out_caps) return TBZ_E_ARG;
+  if ((r = ix_check_args(ctx, ix, in_len, n, firsts, counts, out_offs, results))) return r;
+  if (in_len && !d_in) return TBZ_E_ARG;
+  for (size_t i = 0; i < n && !d_out; i++)
+    if (out_caps[i]) return TBZ_E_ARG;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  IxPlan P;
+  RecCall C;
+  rec_plan(ix, n, firsts, counts, C.runs, P);
+  return rec_run(ctx, ix, d_in, P, C, n, &d_out, out_offs, out_caps, results);
+}
+
+int tbz_inflate_records(tbz_ctx* ctx, const tbz_index* ix, const uint8_t* in, size_t in_len, size_t n, const uint64_t* firsts,
+                        const uint64_t* counts, tbz_alloc_fn alloc, void* user, tbz_result* results) {
+  using namespace tbz;
+  int r;
+  if (ix && ix->delim < 0) return TBZ_E_ARG;
+  if (!alloc) return TBZ_E_ARG;
+  if ((r = ix_check_args(ctx, ix, in_len, n, firsts, counts, results, results))) return r;
+  if (in_len && !in) return TBZ_E_ARG;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  IxPlan P;
+  RecCall C;
+  rec_plan(ix, n, firsts, counts, C.runs, P);
+  // only the spans' input octets go to the device, one after another (as tbz_inflate_ranges packs them) ...
+  std::vector<StagePiece> pin;
+  uint64_t at = 0;
+  for (IxSpan& s : P.spans) {
+    s.d_in_off = at;
+    pin.push_back(StagePiece{(uint8_t*)in + s.in_lo, at, s.in_hi - s.in_lo});
+    at = (at + (s.in_hi - s.in_lo) + 15) & ~15ull;
+  }
+  if ((r = ensure(ctx, ctx->d_in_stage, at + 64))) return r;
+  if ((r = stage_in(ctx, ctx->d_in_stage.p, pin))) return r;
+  if ((r = rec_run(ctx, ix, ctx->d_in_stage.p, P, C, n, &ctx->d_out_stage.p, nullptr, nullptr, results))) return r;
+  ctx->tim.h2d_copies = pin.empty() ? 0u : 1u;
+  // ... and only the runs' octets come back, each into a buffer of its exact length, asked for in run order
+  std::vector<StagePiece> pout;
+  for (size_t i = 0; i < n; i++)
+    if (results[i].out_len) {
+      uint8_t* out = alloc(user, (size_t)results[i].out_len);
+      if (!out) return TBZ_E_NOMEM;
+      pout.push_back(StagePiece{out, C.place[i], results[i].out_len});
     }
   return stage_out(ctx, ctx->d_out_stage.p, pout);
 }

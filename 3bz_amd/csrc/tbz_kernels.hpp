@@ -5743,4 +5743,167 @@ TBZ_KERNEL_WG(256, 1) void tbz_ix_copy(IxCopyParams P) {
 }
 #undef TBZ_IX_REALIGN
 
+// ================================================================================================
+// KR — tbz_rec_count / tbz_rec_locate: records (the seek index's tbz_index_build_records, tbz_inflate_records*).  A
+// record ends with one delimiter octet; the index keeps the number of delimiter octets in front of every point, so the
+// interval that holds a record's end is known without decoding, and these two kernels do the rest over decoded octets
+// in device memory: count the delimiter octets of pieces of at most IX_PIECE octets, and find the j-th of an interval.
+// Both read the octets the way tbz_ix_copy's body does: whole aligned 16-octet lines around a piece (the source is one
+// of the engine's own buffers), the octets of the first and the last line that lie outside the piece masked off.
+// The per-octet test is exact: with x = word ^ (delim in every octet), ((x & 0x7f7f7f7f) + 0x7f7f7f7f) | x has an
+// octet's top bit SET iff that octet of x is not zero — the add cannot carry out of an octet, so no octet's answer
+// depends on its neighbour (the borrow-propagating (x - 0x01010101) & ~x & 0x80808080 reports 00 01 as two matches).
+// ================================================================================================
+struct RecPiece {
+  u64 src;   // octet offset in src_base; any alignment
+  u32 len;   // <= IX_PIECE
+  u32 slot;  // counts[slot] receives the number of octets equal to delim
+};
+struct RecCountParams {
+  const u8* src_base;
+  const RecPiece* pieces;
+  u32* counts;
+  u32 n_pieces;
+  u32 delim4;  // the delimiter in all four octets of a word
+};
+// one query: the interval lies at src_base + src, is len octets long, and the counts of its pieces (cut from its start,
+// IX_PIECE octets each, the last one shorter) are counts[cnt0 ..].  out_pos[query] receives the offset in the interval of
+// its j-th delimiter octet (0-based), or all ones if it holds fewer.
+struct RecQuery {
+  u64 src, len, j;
+  u32 cnt0, pad;
+};
+struct RecLocateParams {
+  const u8* src_base;
+  const RecQuery* queries;
+  const u32* counts;
+  u64* out_pos;
+  u32 n_queries;
+  u32 delim4;
+};
+constexpr u64 REC_NONE = ~0ull;
+
+// the top bit of every octet of w that equals the delimiter
+TBZ_DEV u32 rec_match(u32 w, u32 delim4) {
+  const u32 x = w ^ delim4;
+  return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
+}
+// all ones in the octets of a word whose positions pos .. pos + 3 lie in [0, n)
+TBZ_DEV u32 rec_keep(i64 pos, i64 n) {
+  const i64 lo = pos < 0 ? -pos : 0, hi = n - pos;  // octets [lo, hi) of the word
+  if (lo >= 4 || hi <= lo) return 0u;
+  const u32 above = 0xffffffffu << (8 * (u32)lo);
+  return hi >= 4 ? above : above & (0xffffffffu >> (8 * (u32)(4 - hi)));
+}
+// matches in the aligned 16-octet line `u` of a piece of n octets that starts k octets (0..15) behind `al`
+TBZ_DEV u32 rec_count_line(const u8* al, u32 u, u32 k, u32 n, u32 last, u32 delim4) {
+  const tbz_u32x4 v = *(const tbz_u32x4*)(al + (u64)u * 16);
+  u32 m0 = rec_match(v.x, delim4), m1 = rec_match(v.y, delim4), m2 = rec_match(v.z, delim4), m3 = rec_match(v.w, delim4);
+  if (u == 0 || u == last) {  // (the only lines that can hold octets of other pieces)
+    const i64 p = (i64)u * 16 - (i64)k;
+    m0 &= rec_keep(p, n);
+    m1 &= rec_keep(p + 4, n);
+    m2 &= rec_keep(p + 8, n);
+    m3 &= rec_keep(p + 12, n);
+  }
+  return tbz_popc64(((u64)m0 << 32) | m1) + tbz_popc64(((u64)m2 << 32) | m3);
+}
+
+TBZ_KERNEL_WG(256, 1) void tbz_rec_count(RecCountParams P) {
+  TBZ_SHARED u32 s_wave[4];
+  const u32 r = tbz_block();
+  if (r >= P.n_pieces) return;
+  const u32 w = tbz_wave(), t = w * 64 + tbz_lane();
+  const RecPiece R = P.pieces[r];
+  const u8* s = P.src_base + R.src;
+  const u32 k = (u32)((uintptr_t)s & 15), n = R.len;
+  const u8* al = s - k;
+  const u32 lines = (k + n + 15) >> 4;  // (<= 4097)
+  u32 c = 0;
+  for (u32 u = t; u < lines; u += IX_THREADS) c += rec_count_line(al, u, k, n, lines - 1, P.delim4);
+  c = tbz_wave_incl_scan_u32(c);
+  if (tbz_lane() == 63) s_wave[w] = c;
+  tbz_wg_barrier();
+  if (t == 0) P.counts[R.slot] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
+constexpr u32 REC_CHUNK = 64;  // octets a lane counts per round of the search inside a piece: four aligned lines
+
+TBZ_KERNEL_WG(256, 1) void tbz_rec_locate(RecLocateParams P) {
+  TBZ_SHARED u32 s_wave[2][4];
+  TBZ_SHARED u32 s_hit[2];
+  const u32 qi = tbz_block();
+  if (qi >= P.n_queries) return;
+  const u32 lane = tbz_lane(), w = tbz_wave(), t = w * 64 + lane;
+  const RecQuery Q = P.queries[qi];
+  // ---- the piece that holds delimiter j: every wave walks the interval's piece counts, 64 a step (the same values
+  // in every wave: nothing to hand over)
+  const u64 n_pieces = (Q.len + IX_PIECE - 1) / IX_PIECE;
+  u64 before = 0, piece = REC_NONE;
+  for (u64 base = 0; base < n_pieces; base += 64) {
+    const u32 c = base + lane < n_pieces ? P.counts[Q.cnt0 + base + lane] : 0u;
+    const u32 incl = tbz_wave_incl_scan_u32(c);  // (64 pieces hold at most 2^22 octets)
+    const u64 here = tbz_ballot(before + incl > Q.j);
+    if (here) {
+      const u32 l = tbz_ffs64(here) - 1;
+      piece = base + l;
+      before += tbz_shfl(incl - c, (int)l);
+      break;
+    }
+    before += tbz_shfl(incl, 63);
+  }
+  if (piece == REC_NONE) {
+    if (t == 0) P.out_pos[qi] = REC_NONE;
+    return;
+  }
+  // ---- inside the piece: rounds of 256 lanes x REC_CHUNK octets in octet order, a workgroup scan of the lanes' counts
+  // per round; the lane whose chunk holds the octet names it, and a ballot over the chunk's 64 octets finds it
+  const u8* s = P.src_base + Q.src + piece * IX_PIECE;
+  const u64 left = Q.len - piece * IX_PIECE;
+  const u32 n = left < IX_PIECE ? (u32)left : IX_PIECE;
+  const u32 k = (u32)((uintptr_t)s & 15);
+  const u8* al = s - k;
+  const u32 lines = (k + n + 15) >> 4;
+  const u32 chunks = (lines + 3) >> 2;  // (<= 1025)
+  u32 want = (u32)(Q.j - before);       // ordinal inside the piece
+  bool found = false;
+  for (u32 c0 = 0; c0 < chunks; c0 += IX_THREADS) {
+    const u32 ch = c0 + t;
+    u32 c = 0;
+    if (ch < chunks) {
+#pragma unroll
+      for (u32 i = 0; i < 4; i++)
+        if (ch * 4 + i < lines) c += rec_count_line(al, ch * 4 + i, k, n, lines - 1, P.delim4);
+    }
+    const u32 incl = tbz_wave_incl_scan_u32(c);
+    const u32 par = (c0 / IX_THREADS) & 1;  // (two sets of wave totals: a wave may be one round ahead of another)
+    if (lane == 63) s_wave[par][w] = incl;
+    tbz_wg_barrier();
+    const u32 t0 = s_wave[par][0], t1 = s_wave[par][1], t2 = s_wave[par][2], t3 = s_wave[par][3];
+    const u32 total = t0 + t1 + t2 + t3;
+    if (want < total) {
+      const u32 excl = incl - c + (w > 0 ? t0 : 0u) + (w > 1 ? t1 : 0u) + (w > 2 ? t2 : 0u);
+      if (want >= excl && want < excl + c) {  // exactly one lane of the workgroup
+        s_hit[0] = ch;
+        s_hit[1] = want - excl;
+      }
+      found = true;
+      break;
+    }
+    want -= total;
+  }
+  if (!found) {  // (the counts are of other octets than these: the caller compares them with the index first)
+    if (t == 0) P.out_pos[qi] = REC_NONE;
+    return;
+  }
+  tbz_wg_barrier();
+  const u32 ch = s_hit[0], rank = s_hit[1];
+  const i64 pos = (i64)ch * REC_CHUNK + lane - (i64)k;  // this lane's octet of the chunk, from the piece's start
+  const bool in = pos >= 0 && pos < (i64)n;
+  const u32 octet = in ? al[(u64)ch * REC_CHUNK + lane] : 0u;
+  const bool hit = in && octet == (P.delim4 & 0xffu);
+  const u64 hits = tbz_ballot(hit);
+  if (w == 0 && hit && tbz_popc64(hits & ((1ull << lane) - 1)) == rank) P.out_pos[qi] = piece * IX_PIECE + (u64)pos;
+}
+
 }  // namespace tbz

@@ -127,7 +127,8 @@ typedef struct tbz_timings {
   float h2d_ms;
   float host_decode_ms;
   float d2h_ms;
-  uint32_t reserved4;
+  uint32_t rec_count_us; /* tbz_index_build_records*: device time of the delimiter count pass, microseconds (HIP events
+                            around its launches and the read-back of its counts); 0 after every other call */
 } tbz_timings;
 
 typedef struct tbz_ctx tbz_ctx;
@@ -334,6 +335,51 @@ int tbz_inflate_ranges_device(tbz_ctx* ctx, const tbz_index* index, const void* 
                               tbz_result* results);
 int tbz_inflate_ranges(tbz_ctx* ctx, const tbz_index* index, const uint8_t* in, size_t in_len, size_t n,
                        const uint64_t* offs, const uint64_t* lens, uint8_t* const* outs, tbz_result* results);
+
+/* ---- records: read records i..j of a stream by number ----------------------------------------------
+ * (Additive: TBZ_ABI_VERSION stays 4.)  A delimiter is ONE octet value, 0..255.  Record r of a stream's output is the
+ * octets behind the r-th delimiter octet (record 0 starts at octet 0) up to AND INCLUDING the next delimiter octet;
+ * octets behind the last delimiter form a final record without one.  So n_records = n_delims + (the output is not empty
+ * and does not end in the delimiter), the records concatenate to the output, and an empty output has no records.
+ * tbz_index_build_records[_device] does what tbz_index_build[_device] does and then counts, on the device and over the
+ * output where it still lies, the delimiter octets of every interval: the index keeps delim, n_delims, n_records and per
+ * point the number of delimiter octets in front of it (8 octets per point; there is no per-record table).  delim outside
+ * 0..255: TBZ_E_ARG.  An index built by the plain builders has no records: every record entry point returns TBZ_E_ARG for
+ * it.  tbz_index_records_info: TBZ_E_ARG for an index without records; any out-pointer may be NULL.
+ * tbz_index_export writes an index without records as version 1, exactly as before; one with records as version 2: the
+ * version-1 layout with u32 delim, u32 0, u64 n_delims, u64 n_records, u64 rec_before[n] between crc[n] and the windows.
+ * tbz_index_import refuses (TBZ_E_ARG) a version-2 blob whose delim is above 255, whose pad is not 0, whose rec_before
+ * does not start at 0 or descends, in which an interval or the tail holds more delimiters than octets, whose n_records
+ * is neither n_delims nor n_delims + 1 (or is n_delims + 1 for an empty output), or whose sizes do not add up. */
+int tbz_index_build_records_device(tbz_ctx* ctx, int format, const void* d_in, size_t in_len, size_t spacing, int delim,
+                                   tbz_index** out_index, tbz_result* res);
+int tbz_index_build_records(tbz_ctx* ctx, int format, const uint8_t* in, size_t in_len, size_t spacing, int delim,
+                            tbz_index** out_index, tbz_result* res);
+int tbz_index_records_info(const tbz_index* index, int* delim, size_t* n_records);
+/* n runs of records in one call: run i is records firsts[i] .. firsts[i] + counts[i] - 1, clipped at n_records like
+ * read(2); firsts[i] >= n_records or counts[i] == 0 gives zero octets with status TBZ_FINISHED.  The intervals that hold
+ * a run's first and last octet come from the index alone; runs become spans, and spans are merged, batched, decoded by
+ * ONE engine call per sub-batch and checked against their crc32s exactly as for tbz_inflate_ranges.  Then, still on the
+ * device, the delimiter octets of every decoded interval are counted (a count other than the index's fails the span like a
+ * crc mismatch: TBZ_E_CRC32) and each run's first octet and the octet behind its last are located; only then are octets
+ * delivered.  The host never sees decoded octets other than the delivered ones and never scans octets for delimiters.
+ * results[i]: status TBZ_FINISHED, TBZ_OUTPUT_OVERFLOW or the span's error; out_total = the RUN's full length in octets
+ * (NOT the stream's size, which is what tbz_inflate_ranges reports there); boundary_out = the offset of the run's first
+ * octet in the stream's output; out_len = octets delivered = min(out_total, out_caps[i]) — a run longer than its capacity
+ * delivers its correct prefix with TBZ_OUTPUT_OVERFLOW, as tbz_inflate does; a failed span delivers nothing, with out_len =
+ * out_total = 0; segments, in_consumed and flags bit0 as for tbz_inflate_ranges.
+ * Device variant: run i goes to d_out + out_offs[i].  d_out may be NULL when every capacity is 0: a call with all
+ * capacities 0 is the way to ask for the octet ranges (boundary_out, out_total) of records without moving an octet.
+ * Host variant: alloc(user, n) is called once per run that is delivered, in run order, with its exact length, as
+ * tbz_inflate_gzip_members does; not for failed or empty runs.  Only the spans' input octets go to the device, only the
+ * delivered octets and the result words come back.
+ * TBZ_E_ARG: a context other than the index's, in_len other than the index's, NULL arrays with n > 0, an index without
+ * records.  TBZ_E_UNSUPPORTED with TBZ_HIST=off. */
+int tbz_inflate_records_device(tbz_ctx* ctx, const tbz_index* index, const void* d_in, size_t in_len, size_t n,
+                               const uint64_t* firsts, const uint64_t* counts, void* d_out, const uint64_t* out_offs,
+                               const uint64_t* out_caps, tbz_result* results);
+int tbz_inflate_records(tbz_ctx* ctx, const tbz_index* index, const uint8_t* in, size_t in_len, size_t n,
+                        const uint64_t* firsts, const uint64_t* counts, tbz_alloc_fn alloc, void* user, tbz_result* results);
 
 /* ---- gzip header metadata (host side; no device involved) --------------------------------------
  * What decompress-gzip leaves in the gzip-state's slots while it reads the header (gzip.lisp:110-266:

@@ -39,6 +39,8 @@
    #:decompress-gzip-members
    ;; ---- beyond the reference (its :start / :end select INPUT, api.lisp:23-29): random access into one stream
    #:build-index #:free-index #:decompress-range
+   ;; ---- ... and records of it by number (one delimiter octet ends a record)
+   #:index-records #:decompress-records
    ;; ---- beyond the reference (SURVEY §8e): many independent streams over the GPUs of one node, from ONE Lisp process
    #:*engines* #:open-engines #:close-engines #:decompress-vectors))
 (in-package #:3bz-amd)
@@ -121,6 +123,20 @@
 (cffi:defcfun ("tbz_inflate_ranges_device" %inflate-ranges-device) :int
   (ctx :pointer) (index :pointer) (d-in :pointer) (in-len :size) (n :size) (offs :pointer) (lens :pointer) (d-out :pointer)
   (out-offs :pointer) (results :pointer))
+
+;;; records: the index also counts a delimiter octet per interval; runs of records are read by number
+(cffi:defcfun ("tbz_index_build_records" %index-build-records) :int
+  (ctx :pointer) (format :int) (in :pointer) (in-len :size) (spacing :size) (delim :int) (out-index :pointer) (res :pointer))
+(cffi:defcfun ("tbz_index_build_records_device" %index-build-records-device) :int
+  (ctx :pointer) (format :int) (d-in :pointer) (in-len :size) (spacing :size) (delim :int) (out-index :pointer)
+  (res :pointer))
+(cffi:defcfun ("tbz_index_records_info" %index-records-info) :int (index :pointer) (delim :pointer) (n-records :pointer))
+(cffi:defcfun ("tbz_inflate_records" %inflate-records) :int
+  (ctx :pointer) (index :pointer) (in :pointer) (in-len :size) (n :size) (firsts :pointer) (counts :pointer) (alloc :pointer)
+  (user :pointer) (results :pointer))
+(cffi:defcfun ("tbz_inflate_records_device" %inflate-records-device) :int
+  (ctx :pointer) (index :pointer) (d-in :pointer) (in-len :size) (n :size) (firsts :pointer) (counts :pointer) (d-out :pointer)
+  (out-offs :pointer) (out-caps :pointer) (results :pointer))
 
 (deftype octet () '(unsigned-byte 8))
 (deftype octet-vector () '(simple-array octet (*)))
@@ -396,13 +412,18 @@
         (values output (cffi:foreign-slot-value res '(:struct tbz-result) 'out-len))))))
 
 ;;; ---- random access (no counterpart in 3bz: a stream is decoded from its first block, deflate.lisp:719-722) ----
-(defun build-index (compressed &key (format :zlib) (spacing 0))
+(defun build-index (compressed &key (format :zlib) (spacing 0) delimiter)
   "Decodes COMPRESSED once and returns an index (a foreign pointer; FREE-INDEX releases it): block starts at least SPACING
-octets of output apart (0: 1 MiB), their 32 KiB windows and a crc32 per interval.  A stream that DECOMPRESS-VECTOR would
-not accept signals what DECOMPRESS-VECTOR signals."
+octets of output apart (0: 1 MiB), their 32 KiB windows and a crc32 per interval.  DELIMITER (an octet, 0..255, or a
+character of that code): the index also knows the records that octet ends, for DECOMPRESS-RECORDS.  A stream that
+DECOMPRESS-VECTOR would not accept signals what DECOMPRESS-VECTOR signals."
   (cffi:with-foreign-objects ((res '(:struct tbz-result)) (out :pointer))
     (cffi:with-pointer-to-vector-data (pin compressed)
-      (check-call (%index-build (engine) (format-code format) pin (length compressed) spacing out res) "tbz_index_build"))
+      (if delimiter
+          (check-call (%index-build-records (engine) (format-code format) pin (length compressed) spacing
+                                            (if (characterp delimiter) (char-code delimiter) delimiter) out res)
+                      "tbz_index_build_records")
+          (check-call (%index-build (engine) (format-code format) pin (length compressed) spacing out res) "tbz_index_build")))
     (let ((status (cffi:foreign-slot-value res '(:struct tbz-result) 'status)))
       (when (minusp status) (error "~a" (%strerror status)))
       (unless (zerop status) (error "incomplete ~a stream" format)))
@@ -426,6 +447,34 @@ intervals of INDEX that cover the range are decoded, and only their input octets
             (count (cffi:foreign-slot-value res '(:struct tbz-result) 'out-len)))
         (when (minusp status) (error "~a" (%strerror status)))
         (if (= count (length buffer)) buffer (subseq buffer 0 count))))))
+
+(defun index-records (index)
+  "the delimiter octet and the number of records of INDEX, as two values (an error for an index built without :DELIMITER)"
+  (cffi:with-foreign-objects ((delim :int) (n :size))
+    (check-call (%index-records-info index delim n) "tbz_index_records_info")
+    (values (cffi:mem-ref delim :int) (cffi:mem-ref n :size))))
+
+(defun decompress-records (compressed index first count)
+  "Records FIRST .. FIRST + COUNT - 1 of the stream's OUTPUT with their delimiters, as a fresh octet vector (clipped at the
+last record; no octets when FIRST is not below the number of records).  INDEX comes from (BUILD-INDEX v :DELIMITER d).
+Only the intervals that hold the run are decoded, and the delimiters are counted and located on the device."
+  (let ((*alloc-results* nil))
+    (cffi:with-foreign-objects ((res '(:struct tbz-result)) (f :uint64) (c :uint64))
+      (setf (cffi:mem-ref f :uint64) first
+            (cffi:mem-ref c :uint64) count)
+      (unwind-protect
+           (progn
+             (cffi:with-pointer-to-vector-data (pin compressed)
+               (check-call (%inflate-records (engine) index pin (length compressed) 1 f c (cffi:callback alloc-octets)
+                                             (cffi:null-pointer) res)
+                           "tbz_inflate_records"))
+             (let ((status (cffi:foreign-slot-value res '(:struct tbz-result) 'status)))
+               (when (minusp status) (error "~a" (%strerror status))))
+             (if *alloc-results*
+                 (take-alloc-result (first *alloc-results*))
+                 (make-array 0 :element-type 'octet)))
+        (dolist (cell *alloc-results*)   ; (handed out and not taken: given back)
+          (unless (cffi:null-pointer-p (car cell)) (cffi:foreign-free (car cell))))))))
 
 ;;; ---- every member of a multi-member .gz (SURVEY §8f-4; 3bz stops after the first: gzip.lisp:277-286) ----
 (defun decompress-gzip-members (compressed &key (start 0) (end (length compressed)) (max-members 1048576))
