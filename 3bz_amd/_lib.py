@@ -57,7 +57,7 @@ SYMBOLS = [
     "tbz_index_build", "tbz_index_build_device", "tbz_index_destroy", "tbz_index_info", "tbz_index_points",
     "tbz_index_export", "tbz_index_import", "tbz_inflate_ranges", "tbz_inflate_ranges_device",
     "tbz_index_build_records", "tbz_index_build_records_device", "tbz_index_records_info", "tbz_inflate_records",
-    "tbz_inflate_records_device",
+    "tbz_inflate_records_device", "tbz_search_records", "tbz_search_records_device",
 ]
 
 
@@ -138,6 +138,9 @@ def load(path=None):
     L.tbz_index_records_info.argtypes = [vp, C.POINTER(C.c_int), szp]
     L.tbz_inflate_records_device.argtypes = [vp, vp, vp, sz, sz, u64p, u64p, vp, u64p, u64p, C.POINTER(Result)]
     L.tbz_inflate_records.argtypes = [vp, vp, vp, sz, sz, u64p, u64p, ALLOC_FN, vp, C.POINTER(Result)]
+    u8p = C.c_char_p
+    L.tbz_search_records_device.argtypes = [vp, vp, vp, sz, u8p, sz, sz, sz, u64p, sz, u64p, C.POINTER(Result)]
+    L.tbz_search_records.argtypes = [vp, vp, vp, sz, u8p, sz, sz, sz, u64p, sz, u64p, C.POINTER(Result)]
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the ABI is incomplete
     return L

@@ -374,6 +374,38 @@ class Engine:
                                                         a(out_offs), a(out_caps), res))
         return list(res)[:n]
 
+    # ---- search: which records hold a pattern
+    SEARCH_MAX_PATTERN = 32
+
+    def _search(self, fn, index, src, in_len, pattern, first, count, max_hits):
+        pattern = bytes(pattern)
+        if not 1 <= len(pattern) <= self.SEARCH_MAX_PATTERN:
+            raise ValueError("a pattern is 1 .. %d octets" % self.SEARCH_MAX_PATTERN)
+        n_records = index.records_info()["n_records"]
+        count = n_records if count is None else count
+        searched = max(0, min(count, n_records - first))
+        max_hits = searched if max_hits is None else max_hits
+        room = min(max_hits, searched)   # (no more numbers can come back than records are searched)
+        nos = (C.c_uint64 * max(1, room))()
+        n_hits, res = C.c_uint64(0), _lib.Result()
+        self._check(fn(self._ctx, index._ix, src, in_len, pattern, len(pattern), first, count, nos if max_hits else None,
+                       max_hits, C.byref(n_hits), C.byref(res)))
+        return list(nos[:min(n_hits.value, room)]), n_hits.value, res
+
+    def search_records(self, index, data, pattern, first=0, count=None, max_hits=None, start=0, end=None):
+        """tbz_search_records: the numbers of the records among first .. first + count - 1 (count None: to the last) that
+        hold `pattern` (bytes of 1 .. 32 octets) wholly inside them, delimiter included: (numbers, n_hits, Result).
+        numbers is ascending and at most max_hits long (None: all); n_hits counts every matching record.  A failed span
+        gives ([], 0, Result with status < 0)."""
+        end = len(data) if end is None else end
+        base = _addr(data)
+        return self._search(self.lib.tbz_search_records, index, (base or 0) + start if base else None, end - start, pattern,
+                            first, count, max_hits)
+
+    def search_records_device(self, index, d_in, in_len, pattern, first=0, count=None, max_hits=None):
+        """tbz_search_records_device: the stream in HBM; otherwise as search_records"""
+        return self._search(self.lib.tbz_search_records_device, index, d_in, in_len, pattern, first, count, max_hits)
+
     def trim(self):
         """release the context's device scratch (it only grows otherwise)"""
         self._check(self.lib.tbz_ctx_trim(self._ctx))
@@ -908,3 +940,22 @@ def decompress_records(compressed, index, runs, engine=None):
         if r.status < 0:
             raise ThreeBzError(r.status, eng.strerror(r.status))
     return outs
+
+
+def grep_records(compressed, index, pattern, first=0, count=None, limit=None, engine=None):
+    """which records hold `pattern` (bytes of 1 .. 32 octets): (list of record numbers, ascending; the number of matching
+    records).  Records first .. first + count - 1 are searched (count None: to the last); at most `limit` numbers are
+    returned, and with limit None the matching records are counted first and then all asked for.  The occurrence lies
+    wholly inside a record, its delimiter included.  decompress_records fetches the lines.  A damaged part of the stream
+    raises ThreeBzError."""
+    eng = engine or index._eng
+
+    def ask(max_hits):
+        nos, n, res = eng.search_records(index, compressed, pattern, first, count, max_hits)
+        if res.status < 0:
+            raise ThreeBzError(res.status, eng.strerror(res.status))
+        return nos, n
+    if limit is None:
+        _, n = ask(0)
+        return ask(n) if n else ([], 0)
+    return ask(limit)

@@ -59,7 +59,8 @@ struct DevBuf {
   X(d_markers2) X(d_kb_fm2) X(d_mark) X(d_hg) X(d_k6s) X(d_bigs) X(d_recs) X(d_kc_tf) \
   X(d_kc_slots) X(d_kc_ends) X(d_kc_link) X(d_kc_fm2) X(d_markers3) X(d_kb_keep) X(d_kb_kcounts) X(d_gz_cands) \
   X(d_gz_count) X(d_gz_tmp) X(d_wide_res) X(d_cold) X(d_cold2) X(d_small_rec) \
-  X(d_bit_off) X(d_ix_span) X(d_ix_recs) X(d_rec_pieces) X(d_rec_queries) X(d_rec_out)
+  X(d_bit_off) X(d_ix_span) X(d_ix_recs) X(d_rec_pieces) X(d_rec_queries) X(d_rec_out) \
+  X(d_srch_pieces) X(d_srch_flags) X(d_srch_hits)
 
 namespace tbz {
 // A few host threads that copy between a caller's (pageable) buffer and the pinned staging buffers: one thread moves
@@ -4275,6 +4276,8 @@ struct RecCall {
   std::vector<RecRun> runs;
   std::vector<uint64_t> place;  // host variant: where run i lies in d_out_stage
   uint64_t placed = 0;
+  // the search: called per sound run once its octets are located (start, len), in the deliver stage, before the copies
+  std::function<int(size_t i, const IxSpan& s)> located;
 };
 static int rec_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& P, RecCall& C, size_t n, void* const* d_out,
                    const uint64_t* out_offs, const uint64_t* out_caps, tbz_result* results) {
@@ -4352,6 +4355,11 @@ static int rec_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, IxPlan& 
       }
     }
     C.placed = need;
+    for (size_t i = 0; i < n && C.located; i++) {
+      const int64_t si = P.span_of[i];
+      if (si < (int64_t)a || si >= (int64_t)b || !P.spans[si].ok) continue;
+      if ((rr = C.located(i, P.spans[si]))) return rr;
+    }
     for (size_t i = 0; i < n; i++) {
       const int64_t si = P.span_of[i];
       if (si < (int64_t)a || si >= (int64_t)b || !P.spans[si].ok || !P.out_len[i]) continue;
@@ -4378,6 +4386,149 @@ static int ix_check_args(tbz_ctx* ctx, const tbz_index* ix, size_t in_len, size_
   if (in_len != ix->in_len) return TBZ_E_ARG;
   if (!ctx->sym_hist) return TBZ_E_UNSUPPORTED;  // (TBZ_HIST=off: no way to reach the window, as for a resumed session)
   return 0;
+}
+
+// ---- search: which records of [first, first + count) hold the pattern.  The range is walked in ascending passes of
+// whole records; a pass is ONE record run through rec_run with capacity 0 (decode, crc, per-interval delimiter counts,
+// locate), and its `located` stage marks and ranks the hits while the octets are still in the span scratch:
+//   pieces of IX_PIECE from the run's start, tbz_rec_count per piece, prefix sums on the host -> each piece's first record
+//   flags (one octet per record) zeroed, tbz_search_mark
+//   tbz_rec_count over the flags ("delimiter" 1), prefix sums on the host -> each flag piece's first rank
+//   tbz_search_emit for the ranks below max_hits into d_srch_hits, which the caller gets in one copy after the last pass
+// A pass takes the intervals [p, q): p holds the delimiter in front of its first record, q is as far as the span's output
+// plus 9 octets per input octet stays within the pool cap (ix_run's rule), and at least as far as the first record's end.
+// Its records are those whose ending delimiter lies in front of point q, so the next pass re-decodes at most interval q - 1.
+// host_in != NULL: every pass stages its span's input octets at the front of d_in_stage.
+static int search_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, const uint8_t* host_in, const uint8_t* pattern, size_t m,
+                      uint64_t first, uint64_t count, uint64_t* rec_nos, uint64_t max_hits, uint64_t* n_hits, tbz_result* res) {
+  memset(res, 0, sizeof *res);
+  res->status = TBZ_FINISHED;
+  *n_hits = 0;
+  for (size_t i = 0; i + 1 < m; i++)
+    if (pattern[i] == ix->delim) return 0;  // (an occurrence would straddle two records)
+  if (first >= ix->n_records || !count) return 0;
+  const uint64_t last = first + std::min<uint64_t>(count, ix->n_records - first) - 1;
+  const size_t np = ix->out_off.size();
+  const uint64_t room_all = std::min<uint64_t>(max_hits, last - first + 1);
+  int r;
+  if (room_all && (r = ensure(ctx, ctx->d_srch_hits, room_all * 8))) return r;
+  SearchMarkParams mark{};
+  mark.m = (u32)m;
+  mark.delim4 = (u32)ix->delim * 0x01010101u;
+  for (size_t i = 0; i < m; i++) mark.pat[i >> 2] |= (u32)pattern[i] << (8 * (i & 3));
+  constexpr size_t MAX_GRID = 1u << 23;  // (x 256 lanes: within a launch's 2^32 threads)
+  uint64_t hits = 0, octets = 0, start0 = 0, segments = 0, consumed = 0;
+  for (uint64_t cur = first; cur <= last;) {
+    const size_t p = cur ? (size_t)(std::upper_bound(ix->rec_before.begin(), ix->rec_before.end(), cur - 1) - ix->rec_before.begin()) - 1 : 0;
+    auto fits = [&](size_t q) {
+      const uint64_t in = (q < np ? (ix->in_bit[q] + 7) / 8 : ix->in_len) - ix->in_bit[p] / 8;
+      const uint64_t exp = (q < np ? ix->out_off[q] : ix->out_total) - ix->out_off[p];
+      return IX_WIN + exp + 256 + in * 9 <= ctx->pool_cap;
+    };
+    size_t q = p + 1;
+    while (q < np && fits(q + 1)) q++;
+    while (q < np && ix->rec_before[q] <= cur) q++;  // (one record longer than the budget is decoded whole)
+    const uint64_t pass_last = q < np ? std::min<uint64_t>(last, ix->rec_before[q] - 1) : last;
+    const uint64_t f = cur, nrec = pass_last - cur + 1, off0 = 0, cap0 = 0;
+    IxPlan P;
+    RecCall C;
+    rec_plan(ix, 1, &f, &nrec, C.runs, P);
+    const void* src_in = d_in;
+    if (host_in) {
+      IxSpan& s = P.spans[0];
+      s.d_in_off = 0;
+      std::vector<StagePiece> pin{StagePiece{(uint8_t*)host_in + s.in_lo, 0, s.in_hi - s.in_lo}};
+      if ((r = ensure(ctx, ctx->d_in_stage, (s.in_hi - s.in_lo) + 64))) return r;
+      if ((r = stage_in(ctx, ctx->d_in_stage.p, pin))) return r;
+      src_in = ctx->d_in_stage.p;
+    }
+    C.located = [&](size_t, const IxSpan& s) -> int {
+      const RecRun& R = C.runs[0];
+      if (!R.len) return TBZ_E_INTERNAL;  // (a record with its delimiter, or the non-empty rest of the stream)
+      int rr;
+      std::vector<RecPiece> pieces;
+      std::vector<uint32_t> counts;
+      std::vector<uint64_t> none;
+      const uint64_t src0 = s.out_base + (R.start - ix->out_off[s.p]);
+      rec_cut(pieces, src0, R.len);
+      if ((rr = rec_scan(ctx, ctx->d_ix_span.p, ix->delim, pieces, {}, counts, none))) return rr;
+      std::vector<SearchPiece> sp(pieces.size());
+      uint64_t sum = 0;
+      for (size_t j = 0; j < pieces.size(); j++) {
+        sp[j] = SearchPiece{pieces[j].src, sum, pieces[j].len, 0u};
+        sum += counts[j];
+      }
+      // every flag index is at most the delimiters of the run: the counts must be what the index says, or a store could
+      // go behind the flags
+      if (sum != nrec - (R.to_end ? 1 : 0)) return TBZ_E_INTERNAL;
+      const uint64_t flag_bytes = (nrec + 15) & ~15ull;
+      if ((rr = ensure(ctx, ctx->d_srch_flags, flag_bytes + 64))) return rr;
+      TBZ_HIP(hipMemsetAsync(ctx->d_srch_flags.p, 0, flag_bytes, ctx->stream));
+      if ((rr = upload(ctx, ctx->d_srch_pieces, sp))) return rr;
+      for (size_t a = 0; a < sp.size(); a += MAX_GRID) {
+        const size_t cnt = std::min(MAX_GRID, sp.size() - a);
+        SearchMarkParams mp = mark;
+        mp.src_base = (const u8*)ctx->d_ix_span.p;
+        mp.pieces = (const SearchPiece*)ctx->d_srch_pieces.p + a;
+        mp.end = src0 + R.len;
+        mp.flags = (u8*)ctx->d_srch_flags.p;
+        mp.n_pieces = (u32)cnt;
+        TBZ_LAUNCH_WG(tbz_search_mark, cnt, IX_THREADS, ctx->stream, mp);
+      }
+      TBZ_HIP(hipGetLastError());
+      // the set flags per piece of the flag array (the read-back also ends the mark: its piece list is free again)
+      pieces.clear();
+      rec_cut(pieces, 0, nrec);
+      if ((rr = rec_scan(ctx, ctx->d_srch_flags.p, 1, pieces, {}, counts, none))) return rr;
+      const uint64_t done = std::min(hits, room_all), room = room_all - done;
+      sp.clear();
+      sum = 0;
+      for (size_t j = 0; j < pieces.size(); j++) {
+        if (counts[j] && sum < room) sp.push_back(SearchPiece{pieces[j].src, sum, pieces[j].len, 0u});
+        sum += counts[j];
+      }
+      hits += sum;
+      if (sp.empty()) return 0;
+      // (sp is pageable memory: hipMemcpyAsync has taken its octets when it returns, as for ix_copy's piece list, so sp
+      // may go out of scope before the emit has run; ix_run synchronises the stream after this stage)
+      if ((rr = upload(ctx, ctx->d_srch_pieces, sp))) return rr;
+      for (size_t a = 0; a < sp.size(); a += MAX_GRID) {
+        const size_t cnt = std::min(MAX_GRID, sp.size() - a);
+        SearchEmitParams ep{(const u8*)ctx->d_srch_flags.p, (const SearchPiece*)ctx->d_srch_pieces.p + a,
+                            (u64*)ctx->d_srch_hits.p + done, cur, room, (u32)cnt, 0u};
+        TBZ_LAUNCH_WG(tbz_search_emit, cnt, IX_THREADS, ctx->stream, ep);
+      }
+      TBZ_HIP(hipGetLastError());
+      return 0;
+    };
+    void* d_out = nullptr;
+    tbz_result pr;
+    if ((r = rec_run(ctx, ix, src_in, P, C, 1, &d_out, &off0, &cap0, &pr))) return r;
+    segments += pr.segments;
+    consumed += pr.in_consumed;
+    res->segments = (uint32_t)segments;
+    res->in_consumed = consumed;
+    if (!P.spans[0].ok) {  // nothing of the earlier passes is handed out
+      res->status = pr.status;
+      return 0;
+    }
+    if (cur == first) start0 = C.runs[0].start;
+    octets += C.runs[0].len;
+    cur = pass_last + 1;
+  }
+  const uint64_t got = std::min(hits, room_all);
+  if (got && (r = read_back(ctx, rec_nos, ctx->d_srch_hits.p, got * 8))) return r;
+  *n_hits = hits;
+  res->out_total = octets;
+  res->boundary_out = start0;
+  res->flags = 1u;
+  return 0;
+}
+static int search_check_args(tbz_ctx* ctx, const tbz_index* ix, size_t in_len, const uint8_t* pattern, size_t pattern_len,
+                             const uint64_t* rec_nos, size_t max_hits, const uint64_t* n_hits, const tbz_result* res) {
+  if (!pattern || !pattern_len || pattern_len > TBZ_SEARCH_MAX_PATTERN || !n_hits || !res || (max_hits && !rec_nos)) return TBZ_E_ARG;
+  if (ix && ix->delim < 0) return TBZ_E_ARG;
+  return ix_check_args(ctx, ix, in_len, 0, nullptr, nullptr, nullptr, nullptr);
 }
 }  // namespace tbz
 
@@ -4801,6 +4952,28 @@ int tbz_inflate_records(tbz_ctx* ctx, const tbz_index* ix, const uint8_t* in, si
       pout.push_back(StagePiece{out, C.place[i], results[i].out_len});
     }
   return stage_out(ctx, ctx->d_out_stage.p, pout);
+}
+
+int tbz_search_records_device(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, size_t in_len, const uint8_t* pattern,
+                              size_t pattern_len, size_t first, size_t count, uint64_t* rec_nos, size_t max_hits, uint64_t* n_hits,
+                              tbz_result* res) {
+  using namespace tbz;
+  int r;
+  if ((r = search_check_args(ctx, ix, in_len, pattern, pattern_len, rec_nos, max_hits, n_hits, res))) return r;
+  if (in_len && !d_in) return TBZ_E_ARG;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  return search_run(ctx, ix, d_in, nullptr, pattern, pattern_len, first, count, rec_nos, max_hits, n_hits, res);
+}
+
+int tbz_search_records(tbz_ctx* ctx, const tbz_index* ix, const uint8_t* in, size_t in_len, const uint8_t* pattern,
+                       size_t pattern_len, size_t first, size_t count, uint64_t* rec_nos, size_t max_hits, uint64_t* n_hits,
+                       tbz_result* res) {
+  using namespace tbz;
+  int r;
+  if ((r = search_check_args(ctx, ix, in_len, pattern, pattern_len, rec_nos, max_hits, n_hits, res))) return r;
+  if (in_len && !in) return TBZ_E_ARG;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  return search_run(ctx, ix, nullptr, in, pattern, pattern_len, first, count, rec_nos, max_hits, n_hits, res);
 }
 
 }  // extern "C"

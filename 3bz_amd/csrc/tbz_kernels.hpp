@@ -5906,4 +5906,168 @@ TBZ_KERNEL_WG(256, 1) void tbz_rec_locate(RecLocateParams P) {
   if (w == 0 && hit && tbz_popc64(hits & ((1ull << lane) - 1)) == rank) P.out_pos[qi] = piece * IX_PIECE + (u64)pos;
 }
 
+// ================================================================================================
+// KS — tbz_search_mark / tbz_search_emit: which records of a run hold a pattern (tbz_search_records*).  The run is
+// whole records, decoded and checked, in the span scratch; the host has counted the delimiter octets of its pieces
+// (tbz_rec_count) and prefix-summed them, so every piece knows the ordinal, within the run, of the record its first
+// octet belongs to.  tbz_search_mark sets flags[ordinal of the record] = 1 for every occurrence of the pattern: one
+// octet per record, every writer stores the same value and the store is idempotent, so there is no atomic and no
+// bitmap word that two workgroups would have to share.  The host counts the set flags per piece of the flag array
+// (tbz_rec_count again, "delimiter" 1), prefix-sums them, and tbz_search_emit writes first_record + index of every set
+// flag to hits[its rank], ascending, as long as the rank is below the room left.
+// Both read like tbz_rec_locate inside a piece: rounds of 256 lanes x REC_CHUNK octets in octet order, whole aligned
+// 16-octet lines, the octets of the first and the last line outside the piece masked off, a workgroup scan of the
+// lanes' counts per round with a carry across rounds.  A lane's chunk becomes two 64-bit masks (octets equal to the
+// pattern's first octet: the candidates; delimiter octets), so a candidate's record is the carry plus the popcount of
+// the delimiter mask in front of it.  Candidates are verified word by word against the pattern (eight words by value:
+// constant indices, no scratch); a pattern whose first octet never occurs costs one read of the run, and one that is
+// a candidate everywhere costs at most m compares per octet.  An occurrence may end in the next piece (the same
+// buffer) but never at or behind the run's end: those octets are the next record's, or slack.  The host refuses
+// patterns with a delimiter in front of their last octet, so an occurrence inside the run lies inside one record.
+// ================================================================================================
+struct SearchPiece {
+  u64 src;   // octet offset in src_base (mark) / in the flag array (emit); any alignment
+  u64 base;  // mark: ordinal in the run of the record of the piece's first octet; emit: set flags in front of the piece
+  u32 len;   // <= IX_PIECE
+  u32 pad;
+};
+struct SearchMarkParams {
+  const u8* src_base;
+  const SearchPiece* pieces;
+  u64 end;     // offset in src_base of the octet behind the run's last
+  u8* flags;   // one octet per record of the run, zeroed
+  u32 n_pieces;
+  u32 m;       // 1 .. 32
+  u32 delim4;
+  u32 pat[8];  // the pattern, little-endian words, zero behind its last octet
+};
+struct SearchEmitParams {
+  const u8* flags;
+  const SearchPiece* pieces;
+  u64* hits;
+  u64 first_record;  // the record of flags[0]
+  u64 room;          // ranks below this are written
+  u32 n_pieces;
+  u32 pad;
+};
+
+// bit j: octet j of the word matched (rec_match's top bits, packed)
+TBZ_DEV u32 search_bits4(u32 mm) {
+  u32 x = mm >> 7;
+  x |= x >> 7;
+  x |= x >> 14;
+  return x & 0xfu;
+}
+// one bit per octet of the aligned 16-octet line `u` of a piece (n octets, k behind `al`): equal to a4's octet / to b4's
+TBZ_DEV void search_line(const u8* al, u32 u, u32 k, u32 n, u32 last, u32 a4, u32 b4, u32& ma, u32& mb) {
+  const tbz_u32x4 v = *(const tbz_u32x4*)(al + (u64)u * 16);
+  u32 a0 = rec_match(v.x, a4), a1 = rec_match(v.y, a4), a2 = rec_match(v.z, a4), a3 = rec_match(v.w, a4);
+  u32 b0 = rec_match(v.x, b4), b1 = rec_match(v.y, b4), b2 = rec_match(v.z, b4), b3 = rec_match(v.w, b4);
+  if (u == 0 || u == last) {
+    const i64 p = (i64)u * 16 - (i64)k;
+    const u32 k0 = rec_keep(p, n), k1 = rec_keep(p + 4, n), k2 = rec_keep(p + 8, n), k3 = rec_keep(p + 12, n);
+    a0 &= k0; a1 &= k1; a2 &= k2; a3 &= k3;
+    b0 &= k0; b1 &= k1; b2 &= k2; b3 &= k3;
+  }
+  ma = search_bits4(a0) | (search_bits4(a1) << 4) | (search_bits4(a2) << 8) | (search_bits4(a3) << 12);
+  mb = search_bits4(b0) | (search_bits4(b1) << 4) | (search_bits4(b2) << 8) | (search_bits4(b3) << 12);
+}
+// ... of chunk `ch` (four lines): bit j is the octet at al + ch * REC_CHUNK + j
+TBZ_DEV void search_chunk(const u8* al, u32 ch, u32 k, u32 n, u32 lines, u32 a4, u32 b4, u64& A, u64& B) {
+  A = 0;
+  B = 0;
+#pragma unroll
+  for (u32 i = 0; i < 4; i++)
+    if (ch * 4 + i < lines) {
+      u32 ma, mb;
+      search_line(al, ch * 4 + i, k, n, lines - 1, a4, b4, ma, mb);
+      A |= (u64)ma << (16 * i);
+      B |= (u64)mb << (16 * i);
+    }
+}
+// the workgroup's exclusive scan of c in lane order, and the total, over one set of wave totals
+TBZ_DEV u32 search_wg_scan(u32 (*s_wave)[4], u32 par, u32 c, u32& total) {
+  const u32 w = tbz_wave();
+  const u32 incl = tbz_wave_incl_scan_u32(c);
+  if (tbz_lane() == 63) s_wave[par][w] = incl;
+  tbz_wg_barrier();
+  const u32 t0 = s_wave[par][0], t1 = s_wave[par][1], t2 = s_wave[par][2], t3 = s_wave[par][3];
+  total = t0 + t1 + t2 + t3;
+  return incl - c + (w > 0 ? t0 : 0u) + (w > 1 ? t1 : 0u) + (w > 2 ? t2 : 0u);
+}
+// out[0 .. m) == pattern?  q + m lies within the run; the last word's octets behind m are read (the buffer's slack at
+// most) and masked
+TBZ_DEV bool search_verify(const u8* q, const u32 (&pat)[8], u32 m) {
+  bool ok = true;
+#pragma unroll
+  for (u32 i = 0; i < 8; i++)
+    if (ok && i * 4 < m) {
+      const u8* p = q + i * 4;
+      const u32 w = (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24);
+      const u32 left = m - i * 4;
+      const u32 keep = left >= 4 ? 0xffffffffu : (1u << (8 * left)) - 1u;
+      ok = ((w ^ pat[i]) & keep) == 0;
+    }
+  return ok;
+}
+
+TBZ_KERNEL_WG(256, 1) void tbz_search_mark(SearchMarkParams P) {
+  TBZ_SHARED u32 s_wave[2][4];
+  const u32 r = tbz_block();
+  if (r >= P.n_pieces) return;
+  const u32 t = tbz_wave() * 64 + tbz_lane();
+  const SearchPiece R = P.pieces[r];
+  const u8* s = P.src_base + R.src;
+  const u32 k = (u32)((uintptr_t)s & 15), n = R.len;
+  const u8* al = s - k;
+  const u32 lines = (k + n + 15) >> 4;
+  const u32 chunks = (lines + 3) >> 2;  // (<= 1025)
+  const u32 first4 = (P.pat[0] & 0xffu) * 0x01010101u;
+  const u64 al_off = R.src - k;  // `al` as an offset in src_base
+  u64 carry = R.base;
+  for (u32 c0 = 0; c0 < chunks; c0 += IX_THREADS) {
+    const u32 ch = c0 + t;
+    u64 cand = 0, dl = 0;
+    if (ch < chunks) search_chunk(al, ch, k, n, lines, first4, P.delim4, cand, dl);
+    u32 total;
+    const u32 excl = search_wg_scan(s_wave, (c0 / IX_THREADS) & 1, tbz_popc64(dl), total);
+    while (cand) {  // (lane-private: no collective inside)
+      const u32 b = tbz_ffs64(cand) - 1;
+      cand &= cand - 1;
+      const u64 at = (u64)ch * REC_CHUNK + b;  // from `al`
+      if (al_off + at + P.m <= P.end && search_verify(al + at, P.pat, P.m))
+        P.flags[carry + excl + tbz_popc64(dl & ((1ull << b) - 1))] = 1;
+    }
+    carry += total;
+  }
+}
+
+TBZ_KERNEL_WG(256, 1) void tbz_search_emit(SearchEmitParams P) {
+  TBZ_SHARED u32 s_wave[2][4];
+  const u32 r = tbz_block();
+  if (r >= P.n_pieces) return;
+  const u32 t = tbz_wave() * 64 + tbz_lane();
+  const SearchPiece R = P.pieces[r];
+  const u8* s = P.flags + R.src;
+  const u32 k = (u32)((uintptr_t)s & 15), n = R.len;
+  const u8* al = s - k;
+  const u32 lines = (k + n + 15) >> 4;
+  const u32 chunks = (lines + 3) >> 2;
+  u64 carry = R.base;
+  for (u32 c0 = 0; c0 < chunks; c0 += IX_THREADS) {
+    const u32 ch = c0 + t;
+    u64 set = 0, same = 0;
+    if (ch < chunks) search_chunk(al, ch, k, n, lines, 0x01010101u, 0x01010101u, set, same);
+    u32 total;
+    const u32 excl = search_wg_scan(s_wave, (c0 / IX_THREADS) & 1, tbz_popc64(set), total);
+    u64 rank = carry + excl;
+    while (set && rank < P.room) {
+      const u32 b = tbz_ffs64(set) - 1;
+      set &= set - 1;
+      P.hits[rank++] = P.first_record + R.src + ((u64)ch * REC_CHUNK + b - k);
+    }
+    carry += total;
+  }
+}
+
 }  // namespace tbz

@@ -381,6 +381,45 @@ int tbz_inflate_records_device(tbz_ctx* ctx, const tbz_index* index, const void*
 int tbz_inflate_records(tbz_ctx* ctx, const tbz_index* index, const uint8_t* in, size_t in_len, size_t n,
                         const uint64_t* firsts, const uint64_t* counts, tbz_alloc_fn alloc, void* user, tbz_result* results);
 
+/* ---- search: which records hold a pattern ------------------------------------------------------------
+ * (Additive: TBZ_ABI_VERSION stays 4.)  Records first .. first + count - 1 of an index with records are searched, clipped
+ * at n_records like read(2); first >= n_records or count == 0 gives *n_hits = 0 with status TBZ_FINISHED.  The pattern is
+ * 1 .. TBZ_SEARCH_MAX_PATTERN octets, compared octet for octet.
+ * Match rule: with b[r] the offset of record r's first octet in the output, record r is the octets [b[r], b[r+1]), its
+ * delimiter included, and it matches iff there is an o with b[r] <= o, o + pattern_len <= b[r+1] and
+ * out[o .. o + pattern_len) == pattern: the occurrence lies wholly inside the record.  So a pattern that ends in the
+ * delimiter matches at record ends; the one-octet pattern that is the delimiter matches every record that has one; a
+ * pattern that holds the delimiter anywhere but in its last octet can match nothing, which is decided on the host without
+ * decoding (*n_hits = 0, TBZ_FINISHED, res->segments == 0); and an occurrence in a record outside [first, first + count)
+ * is never reported, although its octets may be decoded (the interval in front of the range, the rest of the last one).
+ * The range is walked in ascending passes of whole records: a pass takes the intervals from the one that holds the
+ * delimiter in front of its first record as far as its span's output plus 9 octets per input octet stays within the
+ * context's pool cap (at least one interval, and always the whole of its first record), is decoded and checked exactly
+ * as a run of tbz_inflate_records with capacity 0, and is searched on the device where it lies.
+ * (The pool cap bounds a pass's decode.  Its flag array, one octet per record of the pass, and the staged hits, 8 octets
+ * per min(max_hits, records searched), are device memory on top of that.)
+ * Outputs: *n_hits = the number of matching records among those searched, also those beyond max_hits;
+ * rec_nos[0 .. min(*n_hits, max_hits)) = their numbers in ascending order, nothing behind that is written;
+ * max_hits == 0 with rec_nos == NULL counts only.  pattern, rec_nos and n_hits are host memory in both variants.
+ * ONE result record for the call: status TBZ_FINISHED, or the first failed span's error (the decode's TBZ_E_*, or
+ * TBZ_E_CRC32 for an interval whose crc or delimiter count is not the index's) — then *n_hits = 0 and nothing is written
+ * to rec_nos: hits are staged on the device until the last pass is sound; out_total = the octets of the records searched;
+ * boundary_out = the offset of the first searched record's first octet; out_len = 0; segments = intervals decoded and
+ * in_consumed = input octets read, both summed over the passes (an interval decoded by two passes counts twice); flags
+ * bit0 = every decoded interval was checked.
+ * Host variant: only the spans' input octets go to the device, only the hit numbers and the result words come back; the
+ * host never sees a decoded octet and never scans octets (it sums per-piece counts).
+ * TBZ_E_ARG: pattern_len 0 or above TBZ_SEARCH_MAX_PATTERN, a NULL pattern, n_hits or res, a NULL rec_nos with
+ * max_hits > 0, a context other than the index's, in_len other than the index's, an index without records.
+ * TBZ_E_UNSUPPORTED with TBZ_HIST=off. */
+#define TBZ_SEARCH_MAX_PATTERN 32
+int tbz_search_records_device(tbz_ctx* ctx, const tbz_index* index, const void* d_in, size_t in_len, const uint8_t* pattern,
+                              size_t pattern_len, size_t first, size_t count, uint64_t* rec_nos, size_t max_hits,
+                              uint64_t* n_hits, tbz_result* res);
+int tbz_search_records(tbz_ctx* ctx, const tbz_index* index, const uint8_t* in, size_t in_len, const uint8_t* pattern,
+                       size_t pattern_len, size_t first, size_t count, uint64_t* rec_nos, size_t max_hits, uint64_t* n_hits,
+                       tbz_result* res);
+
 /* ---- gzip header metadata (host side; no device involved) --------------------------------------
  * What decompress-gzip leaves in the gzip-state's slots while it reads the header (gzip.lisp:110-266:
  * compression-method, flags, mtime, compression level, operating system, extra / name / comment fields, header CRC).

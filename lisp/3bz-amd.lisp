@@ -41,6 +41,8 @@
    #:build-index #:free-index #:decompress-range
    ;; ---- ... and records of it by number (one delimiter octet ends a record)
    #:index-records #:decompress-records
+   ;; ---- ... and the numbers of the records that hold a pattern
+   #:search-records
    ;; ---- beyond the reference (SURVEY §8e): many independent streams over the GPUs of one node, from ONE Lisp process
    #:*engines* #:open-engines #:close-engines #:decompress-vectors))
 (in-package #:3bz-amd)
@@ -137,6 +139,10 @@
 (cffi:defcfun ("tbz_inflate_records_device" %inflate-records-device) :int
   (ctx :pointer) (index :pointer) (d-in :pointer) (in-len :size) (n :size) (firsts :pointer) (counts :pointer) (d-out :pointer)
   (out-offs :pointer) (out-caps :pointer) (results :pointer))
+;;; search: the numbers of the records that hold a pattern of 1 .. 32 octets, found on the device
+(cffi:defcfun ("tbz_search_records" %search-records) :int
+  (ctx :pointer) (index :pointer) (in :pointer) (in-len :size) (pattern :pointer) (pattern-len :size) (first :size)
+  (count :size) (rec-nos :pointer) (max-hits :size) (n-hits :pointer) (res :pointer))
 
 (deftype octet () '(unsigned-byte 8))
 (deftype octet-vector () '(simple-array octet (*)))
@@ -475,6 +481,36 @@ Only the intervals that hold the run are decoded, and the delimiters are counted
                  (make-array 0 :element-type 'octet)))
         (dolist (cell *alloc-results*)   ; (handed out and not taken: given back)
           (unless (cffi:null-pointer-p (car cell)) (cffi:foreign-free (car cell))))))))
+
+(defun search-records (compressed index pattern &key (first 0) count limit)
+  "The numbers of the records of the stream's OUTPUT that hold PATTERN (an octet vector of 1 .. 32 octets), ascending, as a
+vector of (unsigned-byte 64), and the number of matching records as the second value.  Records FIRST .. FIRST + COUNT - 1
+are searched (COUNT nil: to the last record); at most LIMIT numbers are returned (nil: the matching records are counted
+first, then all asked for).  The occurrence lies wholly inside a record, its delimiter included.  INDEX comes from
+(BUILD-INDEX v :DELIMITER d); DECOMPRESS-RECORDS fetches the lines.  The search runs on the device: only the input octets
+go there, only the numbers come back."
+  (unless (<= 1 (length pattern) 32) (error "a pattern is 1 .. 32 octets"))
+  (let ((count (or count (nth-value 1 (index-records index))))
+        (pat (coerce pattern 'octet-vector)))
+    (flet ((ask (max-hits)
+             (let ((numbers (make-array max-hits :element-type '(unsigned-byte 64))))
+               (cffi:with-foreign-objects ((res '(:struct tbz-result)) (n-hits :uint64))
+                 (cffi:with-pointer-to-vector-data (pin compressed)
+                   (cffi:with-pointer-to-vector-data (ppat pat)
+                     (cffi:with-pointer-to-vector-data (pnos numbers)
+                       (check-call (%search-records (engine) index pin (length compressed) ppat (length pat) first count
+                                                    (if (zerop max-hits) (cffi:null-pointer) pnos) max-hits n-hits res)
+                                   "tbz_search_records"))))
+                 (let ((status (cffi:foreign-slot-value res '(:struct tbz-result) 'status))
+                       (n (cffi:mem-ref n-hits :uint64)))
+                   (when (minusp status) (error "~a" (%strerror status)))
+                   (values (if (< n max-hits) (subseq numbers 0 n) numbers) n))))))
+      (if limit
+          (ask limit)
+          (let ((n (nth-value 1 (ask 0))))   ; (count first; nothing to fetch when nothing matched)
+            (if (zerop n)
+                (values (make-array 0 :element-type '(unsigned-byte 64)) 0)
+                (ask n)))))))
 
 ;;; ---- every member of a multi-member .gz (SURVEY §8f-4; 3bz stops after the first: gzip.lisp:277-286) ----
 (defun decompress-gzip-members (compressed &key (start 0) (end (length compressed)) (max-members 1048576))
