@@ -52,7 +52,7 @@ struct DevBuf {
 #define TBZ_CTX_POOLS(X) \
   X(d_str_off) X(d_str_len) X(d_tile_first) X(d_tile_counts) X(d_tile_offsets) X(d_markers) X(d_items) X(d_res) \
   X(d_tok) X(d_scratch) X(d_runs) X(d_segs) X(d_groups) X(d_order) X(d_k3_fi) X(d_k3_ni) \
-  X(d_k3_oo) X(d_k3_oc) X(d_k3_sums) X(d_k3_flags) X(d_k3_gscan) X(d_k3_gne) X(d_k3_streams) X(d_k3_glob) \
+  X(d_k3_oo) X(d_k3_oc) X(d_k3_sums) X(d_k3_flags) X(d_k3_gscan) X(d_k3_gne) X(d_k3_streams) X(d_k3_glob) X(d_k3_carry) \
   X(d_redo_items) X(d_redo_res) X(d_k0_slots) X(d_k0_fm) X(d_hdr) X(d_gck) X(d_gchunks) X(d_ck_l1) \
   X(d_tok2) X(d_runs2) X(d_ck_chunks) X(d_ck_parts) X(d_ck_streams) X(d_ck_out) X(d_crc_tab) X(d_in_stage) \
   X(d_out_stage) X(d_kb_tf) X(d_kb_slots) X(d_kb_counts) X(d_kb_offsets) X(d_kb_cands) X(d_kb_fc) X(d_kb_head) \
@@ -162,6 +162,9 @@ struct tbz_ctx {
   hipStream_t stream2 = nullptr;  // the gangs of 64 that take a narrow launch's few LARGE items run beside it (launch_k1)
   hipEvent_t evw[2] = {};
   hipEvent_t ev[12] = {};
+  std::vector<hipEvent_t> ev_k12;  // three per part of a partitioned decode (call_k12): created when first needed
+  int k12_parts = 2;               // env TBZ_K12_PARTS: parts the main launch of a large call is decoded in (0, 1: one launch)
+  size_t k12_min_items = 32768;    // env TBZ_K12_MIN_ITEMS: ... from this many items on
   std::string err;
   tbz_timings tim{};
   uint64_t gang_rounds = 0, gang_valid = 0;  // diagnostics of the last call (K1g)
@@ -675,21 +678,24 @@ static int small_fused_try(tbz_ctx* ctx, int format, const void* d_in, uint64_t 
 
 // groups whose whole output fits a linear LDS window (the common case: flush-delimited segments) run with dynamic LDS
 // sized to the largest of them (max_out octets)
-static void launch_k2_linear(tbz_ctx* ctx, K2Params& k2, size_t n_groups, uint64_t max_out) {
+// (a launch over a range of the device-built tables: n_groups workgroups from group k2.first on, k2.n_groups the
+// range's end, max_out the largest small group of the range; st: the stream, the context's own by default)
+static void launch_k2_linear(tbz_ctx* ctx, K2Params& k2, size_t n_groups, uint64_t max_out, hipStream_t st = nullptr) {
+  if (!st) st = ctx->stream;
   k2.win_bytes = (u32)((max_out + K2_SLACK + 63) & ~63ull);
   ctx->tim.k2_kinds |= ctx->k2_single ? 2u : 1u;
   if (ctx->k2_single)
-    TBZ_LAUNCH_DYN(tbz_k2_lz77_small, n_groups, k2.win_bytes + 2 * K2_TOKBUF + 512, ctx->stream, k2);
+    TBZ_LAUNCH_DYN(tbz_k2_lz77_small, n_groups, k2.win_bytes + 2 * K2_TOKBUF + 512, st, k2);
   else
-    TBZ_LAUNCH_DYN_WG(tbz_k2_lz77_dual, n_groups, 128, k2.win_bytes + 2 * K2_TOKBUF + 512 + 2 * sizeof(K2Hand),
-                      ctx->stream, k2);
+    TBZ_LAUNCH_DYN_WG(tbz_k2_lz77_dual, n_groups, 128, k2.win_bytes + 2 * K2_TOKBUF + 512 + 2 * sizeof(K2Hand), st, k2);
 }
 // the rest take the 32 KiB-history ring kernel (nwg workgroups)
-static void launch_k2_ring(tbz_ctx* ctx, const K2Params& k2, size_t nwg) {
+static void launch_k2_ring(tbz_ctx* ctx, const K2Params& k2, size_t nwg, hipStream_t st = nullptr) {
+  if (!st) st = ctx->stream;
   ctx->tim.k2_kinds |= 4u;
-  if (ctx->k2_single) TBZ_LAUNCH(tbz_k2_lz77, nwg, ctx->stream, k2);
-  else if (ctx->k2_ring2) TBZ_LAUNCH_WG(tbz_k2_lz77_ring2, nwg, 128, ctx->stream, k2);
-  else TBZ_LAUNCH_WG(tbz_k2_lz77_ring3, nwg, 192, ctx->stream, k2);
+  if (ctx->k2_single) TBZ_LAUNCH(tbz_k2_lz77, nwg, st, k2);
+  else if (ctx->k2_ring2) TBZ_LAUNCH_WG(tbz_k2_lz77_ring2, nwg, 128, st, k2);
+  else TBZ_LAUNCH_WG(tbz_k2_lz77_ring3, nwg, 192, st, k2);
 }
 // experiment builds: the linear kernel's counters and records (TBZ_K2_TRACE)
 static void k2_trace(tbz_ctx* ctx) {
@@ -865,6 +871,7 @@ static int hgroups_launch(tbz_ctx* ctx, const std::vector<HGroupSpan>& hgs, K2Pa
 // ==================================================================================================== inflate_core
 // The whole pipeline on device-resident buffers, run as a sequence of stages over one `Call`: the call's arguments,
 // what follows from them, and the state that passes from one stage to the next.  Each stage returns 0 or a TBZ_E_* code.
+constexpr u32 K12_MAX_PARTS = 64;  // most parts a main launch is decoded in (call_k12): K3's verdict slots
 enum { DIST_NONE = 0, DIST_FIRST = 1, DIST_AFTER_OVERFLOW = 2 };  // per stream: a match reaching before its first octet
 struct Call {
   // ---- the arguments
@@ -905,6 +912,7 @@ struct Call {
   float huff_ms = 0;
   // ---- K3: the device layout and its verdict
   bool simple = false;
+  bool k12 = false;  // the call was laid out and decoded in item-range parts (call_k12), results included
   K3Params k3{};  // (k3.n_tiles: K3's tiles)
   K3Global* h_glob = nullptr;  // (pinned read-backs)
   K3Stream* h_k3s = nullptr;
@@ -1012,7 +1020,7 @@ static int call_k0(Call& c) {
   const size_t tiles = c.tiles;
   int r;
   if ((r = record(ctx, 0))) return r;
-  if ((r = pinned(ctx, (n + 5) * 4 + 16 + sizeof(K3Global) + (n + 1) * sizeof(K3Stream)))) return r;  // (read-backs, K0 to K3)
+  if ((r = pinned(ctx, (n + 5) * 4 + 16 + (1 + K12_MAX_PARTS) * sizeof(K3Global) + (n + 1) * sizeof(K3Stream)))) return r;  // (read-backs, K0 to K3)
   if (tiles) {
     const std::vector<uint64_t> h_off(c.in_offs, c.in_offs + n), h_len(c.in_lens, c.in_lens + n);
     if ((r = upload(ctx, ctx->d_str_off, h_off))) return r;
@@ -1326,14 +1334,24 @@ static RunRec* pool_runs(const Call& c, bool fix) {
   return fix ? (RunRec*)c.ctx->d_runs2.p - (c.pool2_base >> RUN_SHIFT) : (RunRec*)c.ctx->d_runs.p - (c.pool_base >> RUN_SHIFT);
 }
 // (the one-lane kernel writes one word per bit at most: its items live in a pool of that density, or bring their own regions)
-static int launch_lane(Call& c, const Item* d_items, SegResult* d_res, size_t n_it, bool fix, bool explicit_items = false) {
+// A main launch decoded in parts (call_k12): the part's items are [slot0, slot0 + n_it) of the call's n_slots items, and
+// d_items / d_res point at the part's first.  What K1 keeps per item-in-launch (K1h's records, the scratch, the parked
+// lists) lives in the item's own slot of the call; the part runs on `stream`, by the flavour chosen for the whole call.
+struct K1Part {
+  size_t slot0, n_slots;
+  hipStream_t stream;
+  int gang;
+};
+static int launch_lane(Call& c, const Item* d_items, SegResult* d_res, size_t n_it, bool fix, bool explicit_items = false,
+                       const K1Part* part = nullptr) {
   tbz_ctx* ctx = c.ctx;
   if (pool_half(c, fix) && !explicit_items) return TBZ_E_INTERNAL;
-  int rr = ensure(ctx, ctx->d_scratch, n_it * (size_t)K1_SCRATCH);
+  int rr = ensure(ctx, ctx->d_scratch, (part ? part->n_slots : n_it) * (size_t)K1_SCRATCH);
   if (rr) return rr;
   K1Params k1{(const u8*)c.d_in, pool_tok(c, fix), d_items, d_res, c.d_markers_cur,
-              (u8*)ctx->d_scratch.p, pool_runs(c, fix), c.d_first_marker, (u32)c.n_mark, (u32)n_it, items_per_wg(n_it), c.resume_abs};
-  TBZ_LAUNCH(tbz_k1_huff_decode, (n_it + k1.items_per_wg - 1) / k1.items_per_wg, ctx->stream, k1);
+              (u8*)ctx->d_scratch.p + (part ? part->slot0 : 0) * (size_t)K1_SCRATCH, pool_runs(c, fix), c.d_first_marker,
+              (u32)c.n_mark, (u32)n_it, items_per_wg(n_it), c.resume_abs};
+  TBZ_LAUNCH(tbz_k1_huff_decode, (n_it + k1.items_per_wg - 1) / k1.items_per_wg, part ? part->stream : ctx->stream, k1);
   return 0;
 }
 static u32 sub_min(const tbz_ctx* ctx) {
@@ -1424,19 +1442,30 @@ static int redo(Call& c, const std::vector<Item>& its, std::vector<SegResult>& r
   }
   return 0;
 }
-static int launch_k1(Call& c, const Item* d_items, SegResult* d_res, size_t n_it, bool fix) {
-  tbz_ctx* ctx = c.ctx;
+// the flavour a launch of n_it items runs as
+static int k1_gang_of(const Call& c, size_t n_it, bool fix) {
   int G = k1_gang(c, n_it);
   if (G == 1 && pool_half(c, fix)) G = 8;  // (a repair launch of many small items into a pool laid out for gangs)
+  return G;
+}
+// the main launch of narrow gangs hands its few large items to gangs of 64 on the second stream (launch_k1)
+static bool k1_wide_beside(const Call& c, int G, bool fix) {
+  return !fix && G > 1 && G <= 16 && wide_for(c.ctx, G, fix) && c.ctx->stream2;
+}
+static int launch_k1(Call& c, const Item* d_items, SegResult* d_res, size_t n_it, bool fix, const K1Part* part = nullptr) {
+  tbz_ctx* ctx = c.ctx;
+  const int G = part ? part->gang : k1_gang_of(c, n_it, fix);
+  [[maybe_unused]] const hipStream_t st = part ? part->stream : ctx->stream;
+  const size_t slot0 = part ? part->slot0 : 0, n_slots = part ? part->n_slots : n_it;
   if (!fix) ctx->tim.k1_gang = (uint32_t)G;
-  if (G == 1) return launch_lane(c, d_items, d_res, n_it, fix);
+  if (G == 1) return launch_lane(c, d_items, d_res, n_it, fix, false, part);
   size_t per = 64 / G, nwg = (n_it + per - 1) / per;
   // A launch of NARROW gangs (short items) declines the few items that are far larger than its mean (SEG_WIDE).
   // Gangs of 64 take exactly those — a second kernel over the same item list on the second stream, every workgroup of
   // which leaves at once unless its item is such a one — BESIDE the narrow launch instead of after the host has read
   // its results (config 5: one 294 Kbit block among 3 548 items: 0.77 + 0.8 ms one after the other).  Their results
   // go to an array of their own (the narrow gang writes SEG_WIDE into the item's record).
-  if (!fix && G <= 16 && wide_for(ctx, G, fix) && ctx->stream2) {  // (gangs of 32: the 65 536 workgroups of config 2 that leave at once cost K1 1 - 2 %: measured)
+  if (!part && k1_wide_beside(c, G, fix)) {  // (gangs of 32: the 65 536 workgroups of config 2 that leave at once cost K1 1 - 2 %: measured)
     int rr = ensure(ctx, ctx->d_wide_res, n_it * sizeof(SegResult));
     if (rr) return rr;
     if ((rr = ensure(ctx, ctx->d_cold2, n_it * (size_t)KG_COLD_STRIDE))) return rr;  // (only the large items' slots are touched)
@@ -1452,14 +1481,17 @@ static int launch_k1(Call& c, const Item* d_items, SegResult* d_res, size_t n_it
   // K1h: every lane parses the first block header of its own item, so that the gangs need not (their leaders
   // would do it with 2 of 64 lanes busy)
   int rr;
-  if ((rr = ensure(ctx, ctx->d_scratch, n_it * (size_t)K1_SCRATCH))) return rr;
-  if ((rr = ensure(ctx, ctx->d_hdr, n_it * sizeof(HdrRec)))) return rr;
-  if (G >= 32 && (rr = ensure(ctx, ctx->d_cold, n_it * (size_t)KG_COLD_STRIDE))) return rr;  // (narrower gangs keep their lists in LDS)
-  K1hParams kh{(const u8*)c.d_in, d_items, (u8*)ctx->d_scratch.p, (HdrRec*)ctx->d_hdr.p, (u32)n_it};
-  if (ctx->k1h) TBZ_LAUNCH(tbz_k1h_headers, (n_it + 63) / 64, ctx->stream, kh);
-  K1gParams kg = k1g_params(c, d_items, d_res, n_it, G, fix, false, (u8*)ctx->d_cold.p);
-  kg.hdr = ctx->k1h ? (const HdrRec*)ctx->d_hdr.p : nullptr;
-  kg.hdr_lens = (const u8*)ctx->d_scratch.p;
+  if ((rr = ensure(ctx, ctx->d_scratch, n_slots * (size_t)K1_SCRATCH))) return rr;
+  if ((rr = ensure(ctx, ctx->d_hdr, n_slots * sizeof(HdrRec)))) return rr;
+  if (G >= 32 && (rr = ensure(ctx, ctx->d_cold, n_slots * (size_t)KG_COLD_STRIDE))) return rr;  // (narrower gangs keep their lists in LDS)
+  u8* const scratch = (u8*)ctx->d_scratch.p + slot0 * (size_t)K1_SCRATCH;
+  HdrRec* const hdr = (HdrRec*)ctx->d_hdr.p + slot0;
+  u8* const cold = ctx->d_cold.p ? (u8*)ctx->d_cold.p + slot0 * (size_t)KG_COLD_STRIDE : nullptr;
+  K1hParams kh{(const u8*)c.d_in, d_items, scratch, hdr, (u32)n_it};
+  if (ctx->k1h) TBZ_LAUNCH(tbz_k1h_headers, (n_it + 63) / 64, st, kh);
+  K1gParams kg = k1g_params(c, d_items, d_res, n_it, G, fix, false, cold);
+  kg.hdr = ctx->k1h ? hdr : nullptr;
+  kg.hdr_lens = scratch;
   kg.wide_bits = wide_for(ctx, G, fix);
 #ifdef TBZ_WAVE_TRACE
   {
@@ -1485,15 +1517,17 @@ static int launch_k1(Call& c, const Item* d_items, SegResult* d_res, size_t n_it
   }
 #endif
   switch (G) {
-    case 8: TBZ_LAUNCH(tbz_k1g8_huff_decode, nwg, ctx->stream, kg); break;
-    case 16: TBZ_LAUNCH(tbz_k1g16_huff_decode, nwg, ctx->stream, kg); break;
-    case 32: TBZ_LAUNCH(tbz_k1g32_huff_decode, nwg, ctx->stream, kg); break;
-    default: TBZ_LAUNCH(tbz_k1g64_huff_decode, nwg, ctx->stream, kg); break;
+    case 8: TBZ_LAUNCH(tbz_k1g8_huff_decode, nwg, st, kg); break;
+    case 16: TBZ_LAUNCH(tbz_k1g16_huff_decode, nwg, st, kg); break;
+    case 32: TBZ_LAUNCH(tbz_k1g32_huff_decode, nwg, st, kg); break;
+    default: TBZ_LAUNCH(tbz_k1g64_huff_decode, nwg, st, kg); break;
   }
   if (c.wide_beside && !fix) TBZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->evw[1], 0));  // what follows needs both
   return 0;
 }
 
+static u32 k12_parts(const Call& c, u32 k3_tiles);
+static int call_k12(Call& c, u32 parts);
 // ---------------------------------------------------------------- K1 main launch (events 2 / 3) + K3 verdict
 // K3 (layout on the device when every item simply lands on its successor): its stream tables go up before
 // K1 so that nothing but two tiny kernels and a 16-byte read-back stand between K1 and the decision
@@ -1523,21 +1557,26 @@ static int call_k1(Call& c) {
     if ((r = ensure(ctx, ctx->d_segs, n_items * sizeof(Seg)))) return r;
     if ((r = ensure(ctx, ctx->d_groups, n_items * sizeof(Group)))) return r;
     if ((r = ensure(ctx, ctx->d_k3_streams, (n + 1) * sizeof(K3Stream)))) return r;
-    if ((r = ensure(ctx, ctx->d_k3_glob, sizeof(K3Global)))) return r;
+    if ((r = ensure(ctx, ctx->d_k3_glob, (1 + K12_MAX_PARTS) * sizeof(K3Global)))) return r;
+    if ((r = ensure(ctx, ctx->d_k3_carry, 3 * 8))) return r;
     c.k3 = K3Params{(const Item*)ctx->d_items.p, (const SegResult*)ctx->d_res.p, (const u32*)ctx->d_k3_fi.p,
                     (const u32*)ctx->d_k3_ni.p, (const u64*)ctx->d_k3_oo.p, (const u64*)ctx->d_k3_oc.p,
                     (u64*)ctx->d_k3_sums.p, (u64*)ctx->d_k3_flags.p, (u64*)ctx->d_k3_gscan.p, (u32*)ctx->d_k3_gne.p,
                     (Seg*)ctx->d_segs.p, (Group*)ctx->d_groups.p, (K3Stream*)ctx->d_k3_streams.p,
-                    (K3Global*)ctx->d_k3_glob.p, (u32)n_items, k3_tiles, (u32)n};
+                    (K3Global*)ctx->d_k3_glob.p, (u32)n_items, k3_tiles, (u32)n, 0, k3_tiles, (u64*)ctx->d_k3_carry.p};
   }
   if ((r = record(ctx, 2))) return r;
+  char* pin_k3 = (char*)ctx->h_pin + (((n + 5) * 4 + 15) & ~(size_t)15);
+  c.h_glob = (K3Global*)pin_k3;
+  c.h_k3s = (K3Stream*)(pin_k3 + sizeof(K3Global));
+  if (try_simple) {
+    const u32 parts = k12_parts(c, k3_tiles);
+    if (parts > 1) return call_k12(c, parts);  // the main launch and K2 in item-range parts (c.k12: done)
+  }
   if ((r = launch_k1(c, (const Item*)ctx->d_items.p, (SegResult*)ctx->d_res.p, n_items, false))) return r;
   TBZ_HIP(hipGetLastError());
   if ((r = record(ctx, 3))) return r;
   ctx->tim.huff_launches = 1;
-  char* pin_k3 = (char*)ctx->h_pin + (((n + 5) * 4 + 15) & ~(size_t)15);
-  c.h_glob = (K3Global*)pin_k3;
-  c.h_k3s = (K3Stream*)(pin_k3 + sizeof(K3Global));
   if (!try_simple) return 0;
   TBZ_LAUNCH(tbz_k3_tile_sums, k3_tiles, ctx->stream, c.k3);
   TBZ_LAUNCH(tbz_k3_scan_tiles, 1, ctx->stream, c.k3);
@@ -1607,6 +1646,7 @@ static int alloc_out(Call& c, const uint64_t& total, hipEvent_t ready = nullptr)
 }
 
 // ---------------------------------------------------------------- device layout + K2, host reads n+1 records
+static int device_layout_results(Call& c);
 static int call_device_layout(Call& c) {
   tbz_ctx* ctx = c.ctx;
   const size_t n = c.n;
@@ -1643,6 +1683,12 @@ static int call_device_layout(Call& c) {
     TBZ_HIP(hipGetLastError());
   }
   if ((r = record(ctx, 5))) return r;
+  return device_layout_results(c);
+}
+// ... what the streams report, from K3's records (ev[7]: they have arrived)
+static int device_layout_results(Call& c) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n;
   TBZ_HIP(hipEventSynchronize(ctx->ev[7]));  // the stream records are here; K2 keeps running
   c.huff_ms = elapsed(ctx, 2, 3);
   ctx->tim.huff_ms = c.huff_ms;
@@ -1665,6 +1711,141 @@ static int call_device_layout(Call& c) {
     fill_result(c, s, S.status, (uint32_t)k.nonempty);
   }
   return 0;
+}
+
+// ---------------------------------------------------------------- the main launch, K3 and K2 in item-range parts
+// K1 and K2 are both bound by instruction issue, and one launch after the other leaves issue slots empty at four places:
+// the tail of K1's last generation of workgroups, K1h's one wave per SIMD, the tiny K3 launches with the host's wait for
+// the verdict between them, and K2's own ramp and tail.  An item's place in the output depends on the sizes of the
+// items before it and on nothing else, K3 is a prefix sum in item order, and the token pool, the run tables and K1's
+// scratch are addressed by position or by item: so items [0, n/P) can be laid out and handed to K2 while K1 is still
+// decoding [n/P, 2n/P).  Parts are cut at multiples of K3_TILE items and alternate over the context's two streams; part
+// p + 1 is enqueued BEFORE the host waits for part p's verdict, so that wait, K3 and the start of K2(p) run under K1(p + 1).
+// (Nothing orders K1(p + 1) behind K1(p): the two share the chip, and K2 of the one that ends first fills the other's
+// tail.  Holding K1(p + 1) back so that K2(p) runs beside all of it was measured and loses — the two kernels are poor
+// neighbours — as do more than two parts: profiles/README.md.)
+//   stream p & 1:  K1h(p) K1g(p) tile_sums(p) [tile scan p - 1 done] scan_tiles(p) -> verdict p (32 octets, pinned)
+//   ... host: verdict p simple ->  [emit p - 1 done] scan_items(p) emit(p) K2(p)     on the same stream, behind them
+// The path is taken where call_device_layout would be (k12_parts); no work is removed, and one part is the one-launch path.
+// A part that is not simple (K3's flag, or an item at or above the floor of the slicing rule, where the decision needs
+// the call's total) ends it: no further K2 is issued, the remaining parts' K1 runs, and the call goes on as after a
+// non-simple verdict — the general host path lays out and decodes everything, behind the K2 parts already enqueued.
+static u32 k12_parts(const Call& c, u32 k3_tiles) {
+  const tbz_ctx* ctx = c.ctx;
+  if (ctx->k12_parts <= 1 || c.size_only || (c.opt && c.opt->alloc) || !c.d_out || c.n_items < ctx->k12_min_items) return 1;
+  if (k1_wide_beside(c, k1_gang_of(c, c.n_items, false), false)) return 1;  // (that launch owns the second stream)
+  const u32 want = std::min<u32>((u32)ctx->k12_parts, K12_MAX_PARTS), per = (k3_tiles + want - 1) / want;
+  return (k3_tiles + per - 1) / per;
+}
+static int call_k12(Call& c, u32 parts) {
+  tbz_ctx* ctx = c.ctx;
+  const size_t n = c.n, n_items = c.n_items;
+  const u32 tiles = c.k3.n_tiles, per = (tiles + parts - 1) / parts;
+  const int G = k1_gang_of(c, n_items, false);
+  const bool zlib_partials = c.format == TBZ_FORMAT_ZLIB && !ctx->k2_single && !ctx->tun.no_fused_adler;
+  int r;
+  while (ctx->ev_k12.size() < 3 * (size_t)parts) {
+    hipEvent_t e;
+    TBZ_HIP(hipEventCreate(&e));
+    ctx->ev_k12.push_back(e);
+  }
+  hipEvent_t* const ev_tiles = ctx->ev_k12.data();   // part p's tile scan is done
+  hipEvent_t* const ev_verdict = ev_tiles + parts;   // ... its K3Global is on the host
+  hipEvent_t* const ev_emit = ev_verdict + parts;    // ... its gscan / gne entries, tables and stream records are written
+  if (zlib_partials) {  // (nothing is allocated once parts are in flight)
+    if ((r = ensure(ctx, ctx->d_gck, n_items * sizeof(CkPartial)))) return r;
+    if ((r = ensure(ctx, ctx->d_gchunks, n_items * sizeof(CkChunk)))) return r;
+  }
+  const hipStream_t S[2] = {ctx->stream, ctx->stream2};
+  TBZ_HIP(hipEventRecord(ctx->evw[0], ctx->stream));  // (the items and K3's stream tables are there)
+  TBZ_HIP(hipStreamWaitEvent(ctx->stream2, ctx->evw[0], 0));
+  K3Global* const h_parts = (K3Global*)(c.h_k3s + (n + 1));
+  K3Global* const d_parts = (K3Global*)ctx->d_k3_glob.p + 1;
+  auto k3_of = [&](u32 p) {
+    K3Params k = c.k3;
+    k.t0 = p * per;
+    k.t1 = std::min(tiles, k.t0 + per);
+    k.glob = d_parts + p;
+    return k;
+  };
+  // K1 over part p and, with_k3, its tile sums, its share of the tile scan and its verdict on the way to the host
+  auto enqueue = [&](u32 p, bool with_k3) -> int {
+    const hipStream_t st = S[p & 1];
+    const K3Params k = k3_of(p);
+    const size_t i0 = (size_t)k.t0 * K3_TILE, i1 = std::min(n_items, (size_t)k.t1 * K3_TILE);
+    const K1Part kp{i0, n_items, st, G};
+    int rr = launch_k1(c, (const Item*)ctx->d_items.p + i0, (SegResult*)ctx->d_res.p + i0, i1 - i0, false, &kp);
+    if (rr) return rr;
+    if (p == parts - 1) {  // K1's span ends here, K2's begins (tbz_timings)
+      TBZ_HIP(hipEventRecord(ctx->ev[3], st));
+      TBZ_HIP(hipEventRecord(ctx->ev[4], st));
+    }
+    if (!with_k3) return 0;
+    TBZ_LAUNCH(tbz_k3_tile_sums, k.t1 - k.t0, st, k);
+    if (p) TBZ_HIP(hipStreamWaitEvent(st, ev_tiles[p - 1], 0));
+    TBZ_LAUNCH(tbz_k3_scan_tiles, 1, st, k);
+    TBZ_HIP(hipEventRecord(ev_tiles[p], st));
+    TBZ_HIP(hipMemcpyAsync(h_parts + p, d_parts + p, sizeof(K3Global), hipMemcpyDeviceToHost, st));
+    TBZ_HIP(hipEventRecord(ev_verdict[p], st));
+    return 0;
+  };
+  // below this no total can make call_k1's rule slice an item; at or above it the decision needs the call's total
+  const uint64_t slice_floor = !ctx->sym_hist ? ~0ull : ctx->tun.slice ? 2 * (uint64_t)std::max(1024, ctx->tun.slice) : 128u << 10;
+  bool ok = true, partials = zlib_partials;
+  ctx->tim.huff_launches = parts;
+  if ((r = enqueue(0, true))) return r;
+  for (u32 p = 0; p < parts && ok; p++) {
+    const hipStream_t st = S[p & 1];
+    if (p + 1 < parts && (r = enqueue(p + 1, true))) return r;  // one ahead: the wait below runs under its K1
+    TBZ_HIP(hipEventSynchronize(ev_verdict[p]));
+    const K3Global g = h_parts[p];
+    if (g.not_simple || g.max_out >= slice_floor) {
+      ok = false;
+      for (u32 q = p + 2; q < parts; q++)
+        if ((r = enqueue(q, false))) return r;
+      break;
+    }
+    const K3Params k = k3_of(p);
+    const u32 i0 = k.t0 * K3_TILE, i1 = (u32)std::min(n_items, (size_t)k.t1 * K3_TILE), n_it = i1 - i0;
+    if (p) TBZ_HIP(hipStreamWaitEvent(st, ev_emit[p - 1], 0));  // (a stream's first item may lie in any earlier part)
+    TBZ_LAUNCH(tbz_k3_scan_items, k.t1 - k.t0, st, k);
+    TBZ_LAUNCH(tbz_k3_emit, k.t1 - k.t0, st, k);
+    TBZ_HIP(hipEventRecord(ev_emit[p], st));
+    if (p == parts - 1) {  // every stream's record is written: they travel while K2 runs
+      TBZ_HIP(hipMemcpyAsync(c.h_k3s, ctx->d_k3_streams.p, (n + 1) * sizeof(K3Stream), hipMemcpyDeviceToHost, st));
+      TBZ_HIP(hipEventRecord(ctx->ev[7], st));
+    }
+    // adler32 partials come from K2 as long as every group so far went through the two-wave kernel; from the first part
+    // with a large group on, the call's checksums are K4's over the output
+    partials = partials && g.n_big == 0;
+    K2Params k2{(const Seg*)ctx->d_segs.p, (const Group*)ctx->d_groups.p, nullptr,
+                (const u8*)c.d_in, (u8*)c.d_out, i1, 0, 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr, 0, i0};
+    if (g.n_big < n_it) {
+      k2.cls = g.n_big ? 1 : 0;
+      if (partials) {
+        k2.gck = (CkPartial*)ctx->d_gck.p;
+        k2.gchunks = (CkChunk*)ctx->d_gchunks.p;
+      }
+      launch_k2_linear(ctx, k2, n_it, g.max_small, st);
+    }
+    if (g.n_big) {
+      k2.win_bytes = 0;
+      k2.cls = g.n_big < n_it ? 2 : 0;
+      launch_k2_ring(ctx, k2, n_it, st);
+    }
+  }
+  TBZ_HIP(hipGetLastError());
+  TBZ_HIP(hipEventRecord(ctx->evw[1], ctx->stream2));  // what follows on the context's stream follows both
+  TBZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->evw[1], 0));
+  if (!ok) {  // the general path decides, as after a non-simple verdict of the whole launch
+    c.simple = false;
+    ctx->tim.k2_kinds = 0;
+    return 0;
+  }
+  if ((r = record(ctx, 5))) return r;
+  c.simple = c.k12 = true;
+  c.fused_adler = partials;
+  return device_layout_results(c);
 }
 
 // ---------------------------------------------------------------- host path: the main launch's results (+ wide, redo)
@@ -2170,7 +2351,8 @@ static int inflate_core(tbz_ctx* ctx, int format, size_t n, const void* d_in, co
   if ((r = call_k0c(c))) return r;         // fixed-Huffman chains
   if ((r = call_pools(c))) return r;       // (.. 1) token pools
   if ((r = call_k1(c))) return r;          // the main launch (events 2 / 3), K3's verdict
-  if (c.simple) {
+  if (c.k12) {                                  // (laid out and decoded part by part: call_k12)
+  } else if (c.simple) {
     if ((r = call_device_layout(c))) return r;  // device layout + K2 (events 4 / 5)
   } else {
     std::vector<SegResult> res;  // the main launch's result per item
@@ -2298,6 +2480,8 @@ int tbz_ctx_create(int device_id, tbz_ctx** out_ctx) {
   if (const char* m = getenv("TBZ_K2_RING")) ctx->k2_ring2 = !strcmp(m, "2");
   if (const char* m = getenv("TBZ_K1H")) ctx->k1h = m[0] != '0';
   if (const char* m = getenv("TBZ_HIST")) ctx->sym_hist = strcmp(m, "off") != 0;
+  if (const char* m = getenv("TBZ_K12_PARTS")) ctx->k12_parts = std::max(0, atoi(m));
+  if (const char* m = getenv("TBZ_K12_MIN_ITEMS")) ctx->k12_min_items = (size_t)std::max(1L, atol(m));
   if (const char* m = getenv("TBZ_POOL_CAP_MIB")) ctx->pool_cap = (uint64_t)std::max(1, atoi(m)) << 20;
   if (const char* m = getenv("TBZ_FIND")) ctx->find_mode = !strcmp(m, "off") ? 0 : !strcmp(m, "always") ? 2 : 1;
   ctx->k1_mode = k1_mode;
@@ -2325,6 +2509,8 @@ void tbz_ctx_destroy(tbz_ctx* ctx) {
   for (auto& ev : ctx->ev)
     if (ev) hipEventDestroy(ev);
   for (auto& ev : ctx->evw)
+    if (ev) hipEventDestroy(ev);
+  for (auto& ev : ctx->ev_k12)
     if (ev) hipEventDestroy(ev);
   if (ctx->stream2) hipStreamDestroy(ctx->stream2);
   if (ctx->stream) hipStreamDestroy(ctx->stream);

@@ -3590,6 +3590,9 @@ struct K2Params {
   u32 n_plain;
   u8* mark_base;
   u64 mark_bias;
+  // ---- launches over a RANGE of the device-built tables (order == nullptr): workgroup b handles group first + b, and
+  // n_groups is the END of the range; segs / groups / gck / gchunks stay indexed by the group's own number
+  u32 first;
 };
 
 template <class W>
@@ -3930,7 +3933,7 @@ TBZ_DEV void k2_resolve(const K2Src& S, u64 pend, u32 rpos, u64 gpos, u32 dofs, 
 
 // which group this workgroup handles; false: none (beyond the list, or filtered out by size class)
 TBZ_DEV bool k2_pick_group(const K2Params& P, u32& gi, Group& g, Seg& sg_guess, u32 at = ~0u) {
-  if (at == ~0u) at = tbz_block();
+  if (at == ~0u) at = tbz_block() + P.first;
   if (at >= P.n_groups) return false;
   gi = P.order ? P.order[at] : at;
   sg_guess = P.segs[gi];  // device-built tables (K3) have segment i in group i: fetched along with the group
@@ -4844,10 +4847,11 @@ struct K3Stream {              // per stream, written by the device
   SegResult last;              // result of the stream's last item (trailer, end position)
   u64 last_start;              // where that item starts (bit): the last flush boundary the chain landed on
 };
-struct K3Global {
+struct K3Global {               // per launch of tbz_k3_scan_tiles: over the tiles of that launch only, but for total_out
   u32 not_simple, n_big;
   u64 max_small;               // largest group that fits the linear K2 window
-  u64 max_out, total_out;      // largest item / all items (octets): the host slices segments that are far too large
+  u64 max_out, total_out;      // largest item / all items up to the launch's last tile (octets): the host slices segments
+                               // that are far too large
 };
 struct K3Params {
   const Item* items;
@@ -4865,10 +4869,14 @@ struct K3Params {
   K3Stream* streams;
   K3Global* glob;
   u32 n_items, n_tiles, n_streams;
+  // ---- the tiles [t0, t1) this launch covers (the whole call: 0, n_tiles).  The call's tiles may be laid out in several
+  // launches in ascending order: the tile scan continues from the totals the launch before it left in `carry`
+  u32 t0, t1;
+  u64* carry;                  // [3]: out_bytes, tok_words, nonempty of the tiles before t1
 };
 
 TBZ_KERNEL void tbz_k3_tile_sums(K3Params P) {
-  const u32 lane = tbz_lane(), t = tbz_block();
+  const u32 lane = tbz_lane(), t = P.t0 + tbz_block();
   u64 so = 0, sw = 0, sn = 0, bad = 0, nbig = 0, mx = 0, mxo = 0;
   for (u32 it = 0; it < K3_TILE / 64; it++) {
     const u32 i = t * K3_TILE + it * 64 + lane;
@@ -4915,18 +4923,23 @@ TBZ_KERNEL void tbz_k3_tile_sums(K3Params P) {
 TBZ_KERNEL void tbz_k3_scan_tiles(K3Params P) {
   const u32 lane = tbz_lane();
   const u32 T1 = P.n_tiles + 1;
+  u64 total_out = 0;
   for (u32 c = 0; c < 3; c++) {
-    u64 carry = 0;
-    for (u32 i = 0; i < P.n_tiles; i += 64) {
-      const u64 v = (i + lane) < P.n_tiles ? P.tile_sums[c * T1 + i + lane] : 0;
+    u64 carry = P.t0 ? P.carry[c] : 0;
+    for (u32 i = P.t0; i < P.t1; i += 64) {
+      const u64 v = (i + lane) < P.t1 ? P.tile_sums[c * T1 + i + lane] : 0;
       const u64 inc = wave_incl_scan_u64(v);
-      if ((i + lane) < P.n_tiles) P.tile_sums[c * T1 + i + lane] = carry + inc - v;
+      if ((i + lane) < P.t1) P.tile_sums[c * T1 + i + lane] = carry + inc - v;
       carry += tbz_shfl64(inc, 63);
     }
-    if (lane == 0) P.tile_sums[c * T1 + P.n_tiles] = carry;
+    if (lane == 0) {
+      P.carry[c] = carry;
+      if (P.t1 == P.n_tiles) P.tile_sums[c * T1 + P.n_tiles] = carry;
+    }
+    if (c == 0) total_out = carry;
   }
   u64 bad = 0, nbig = 0, mx = 0, mxo = 0;
-  for (u32 i = lane; i < P.n_tiles; i += 64) {
+  for (u32 i = P.t0 + lane; i < P.t1; i += 64) {
     bad += P.tile_flags[i];
     nbig += P.tile_flags[P.n_tiles + i];
     const u64 m = P.tile_flags[2 * P.n_tiles + i];
@@ -4949,14 +4962,14 @@ TBZ_KERNEL void tbz_k3_scan_tiles(K3Params P) {
     gl.n_big = (u32)nbig;
     gl.max_small = mx;
     gl.max_out = mxo;
-    gl.total_out = P.tile_sums[P.n_tiles];
+    gl.total_out = total_out;
     *P.glob = gl;
   }
 }
 
 // exclusive scans of out_bytes and of the non-empty flags over all items (tile prefix + in-tile scan in item order)
 TBZ_KERNEL void tbz_k3_scan_items(K3Params P) {
-  const u32 lane = tbz_lane(), t = tbz_block();
+  const u32 lane = tbz_lane(), t = P.t0 + tbz_block();
   u64 carry = P.tile_sums[t];
   u32 carry_ne = (u32)P.tile_sums[2 * (P.n_tiles + 1) + t];
   for (u32 it = 0; it < K3_TILE / 64; it++) {
@@ -4979,9 +4992,10 @@ TBZ_KERNEL void tbz_k3_scan_items(K3Params P) {
   }
 }
 
-// one Seg and one Group per item; the lane of a stream's last item writes the stream's record
+// one Seg and one Group per item; the lane of a stream's last item writes the stream's record (the stream's first item
+// may lie in a tile of an earlier launch: its gscan / gne entries are there by then)
 TBZ_KERNEL void tbz_k3_emit(K3Params P) {
-  const u32 lane = tbz_lane(), t = tbz_block();
+  const u32 lane = tbz_lane(), t = P.t0 + tbz_block();
   const u32 T1 = P.n_tiles + 1;
   for (u32 it = 0; it < K3_TILE / 64; it++) {
     const u32 i = t * K3_TILE + it * 64 + lane;
@@ -5015,7 +5029,7 @@ TBZ_KERNEL void tbz_k3_emit(K3Params P) {
       P.streams[s] = st;
     }
   }
-  if (t == 0 && lane == 0) {  // whole-call totals ride in the slot after the last stream
+  if (t == P.n_tiles - 1 && lane == 0) {  // whole-call totals ride in the slot after the last stream (the last launch's)
     K3Stream tot;
     tot.total_out = P.tile_sums[P.n_tiles];
     tot.tok_words = P.tile_sums[T1 + P.n_tiles];

@@ -101,11 +101,15 @@ typedef struct tbz_result {
  * roofline.kernel from these. */
 typedef struct tbz_timings {
   float scan_ms;     /* K0 scan_markers (count + scan + emit) + K0b block-start finder */
-  float huff_ms;     /* K1 huff_decode (all rounds) */
-  float lz_ms;       /* K2 lz77_resolve (both planes when segments need history they do not hold) */
+  float huff_ms;     /* K1 huff_decode (all rounds).  A main launch decoded in item-range parts (TBZ_K12_PARTS: K2 of a
+                        part runs beside K1 of the next): from the first part's K1h start to the last part's K1 end */
+  float lz_ms;       /* K2 lz77_resolve (both planes when segments need history they do not hold).  Decoded in parts:
+                        from the last part's K1 end to the last K2's end, so that huff_ms + lz_ms is the decode stage's
+                        span on either path (the K2 time hidden under K1 is in huff_ms) */
   float cksum_ms;    /* K4/K5 checksum partials + combine */
   float total_ms;    /* first kernel start .. last kernel end (device time, includes host chain gaps) */
-  uint32_t huff_launches;
+  uint32_t huff_launches; /* K1 launches: the main one (counted once per part it ran as: 1 unless decoded in parts, also
+                             when a part was not simple and the general path took over) + every repair launch */
   uint32_t fixup_rounds;
   uint64_t token_words; /* u16 token words written by K1 (traffic accounting) */
   uint64_t n_segments;
