@@ -6,7 +6,7 @@ The package holds only what the hot path needs: csrc/ (HIP kernels + host engine
 the ctypes binding and the host-side mirror of the reference's API.
 """
 from .api import (Engine, EngineError, Index, ThreeBzError, build_index, decompress, decompress_ranges, decompress_records, decompress_gzip_members, decompress_vector,  # noqa: F401
-                  default_engine, grep_records,
+                  default_engine, grep_fetch, grep_records,
                   finished, input_underrun, make_deflate_state, make_gzip_state, make_octet_pointer_context,
                   make_octet_stream_context, make_octet_vector_context, resync_file_stream, valid_octet_pointer,
                   valid_octet_stream, with_octet_pointer,

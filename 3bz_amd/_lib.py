@@ -58,6 +58,7 @@ SYMBOLS = [
     "tbz_index_export", "tbz_index_import", "tbz_inflate_ranges", "tbz_inflate_ranges_device",
     "tbz_index_build_records", "tbz_index_build_records_device", "tbz_index_records_info", "tbz_inflate_records",
     "tbz_inflate_records_device", "tbz_search_records", "tbz_search_records_device",
+    "tbz_grep_records", "tbz_grep_records_device",
 ]
 
 
@@ -141,6 +142,9 @@ def load(path=None):
     u8p = C.c_char_p
     L.tbz_search_records_device.argtypes = [vp, vp, vp, sz, u8p, sz, sz, sz, u64p, sz, u64p, C.POINTER(Result)]
     L.tbz_search_records.argtypes = [vp, vp, vp, sz, u8p, sz, sz, sz, u64p, sz, u64p, C.POINTER(Result)]
+    L.tbz_grep_records_device.argtypes = [vp, vp, vp, sz, u8p, sz, sz, sz, vp, sz, u64p, u64p, sz, u64p, u64p, C.POINTER(Result)]
+    L.tbz_grep_records.argtypes = [vp, vp, vp, sz, u8p, sz, sz, sz, ALLOC_FN, vp, sz, u64p, u64p, sz, u64p, u64p,
+                                   C.POINTER(Result)]
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the ABI is incomplete
     return L

@@ -406,6 +406,57 @@ class Engine:
         """tbz_search_records_device: the stream in HBM; otherwise as search_records"""
         return self._search(self.lib.tbz_search_records_device, index, d_in, in_len, pattern, first, count, max_hits)
 
+    # ---- grep: the matching records themselves
+    NO_LIMIT = (1 << (8 * C.sizeof(C.c_size_t))) - 1   # SIZE_MAX
+
+    def _grep(self, call, index, pattern, first, count, max_hits):
+        pattern = bytes(pattern)
+        if not 1 <= len(pattern) <= self.SEARCH_MAX_PATTERN:
+            raise ValueError("a pattern is 1 .. %d octets" % self.SEARCH_MAX_PATTERN)
+        n_records = index.records_info()["n_records"]
+        count = n_records if count is None else count
+        searched = max(0, min(count, n_records - first))
+        max_hits = searched if max_hits is None else max_hits
+        room = min(max_hits, searched)
+        nos, offs = (C.c_uint64 * max(1, room))(), (C.c_uint64 * (room + 1))()
+        n_hits, n_out, res = C.c_uint64(0), C.c_uint64(0), _lib.Result()
+        self._check(call(pattern, len(pattern), first, count, nos if max_hits else None, offs if max_hits else None, max_hits,
+                         C.byref(n_hits), C.byref(n_out), C.byref(res)))
+        got = min(n_hits.value, room)
+        ok = max_hits and res.status >= 0
+        return list(nos[:got]) if ok else [], list(offs[:got + 1]) if ok else [], n_out.value, n_hits.value, res
+
+    def grep_fetch(self, index, data, pattern, first=0, count=None, max_hits=None, max_octets=None, start=0, end=None):
+        """tbz_grep_records: search as search_records does and fetch the matching records from the same pass:
+        (numbers, offsets, bytearray, n_hits, Result).  numbers is ascending and at most max_hits long (None: all);
+        offsets has len(numbers) + 1 entries, record j being the octets offsets[j] .. offsets[j + 1] of a buffer that
+        holds them all; the bytearray holds the records delivered, a prefix of whole records of at most max_octets
+        octets (None: no limit), Result.out_len octets long; Result.status is 1 (TBZ_OUTPUT_OVERFLOW) when fewer than
+        len(numbers) records are in it.  A failed span gives ([], [], bytearray(), 0, Result with status < 0)."""
+        end = len(data) if end is None else end
+        base = _addr(data)
+        src = (base or 0) + start if base else None
+        bufs = []
+
+        def alloc(_user, k):
+            bufs.append(bytearray(k))
+            return C.addressof((C.c_char * k).from_buffer(bufs[-1])) if k else 0
+
+        cb = _lib.ALLOC_FN(alloc)
+        cap = self.NO_LIMIT if max_octets is None else max_octets
+        fn = self.lib.tbz_grep_records
+        nos, offs, _, nh, res = self._grep(lambda *a: fn(self._ctx, index._ix, src, end - start, *a[:4], cb, None, cap, *a[4:]),
+                                           index, pattern, first, count, max_hits)
+        return nos, offs, (bufs[0] if bufs else bytearray()), nh, res
+
+    def grep_fetch_device(self, index, d_in, in_len, pattern, d_out, out_cap, first=0, count=None, max_hits=None):
+        """tbz_grep_records_device: the stream and the destination in HBM: (numbers, offsets, n_out, n_hits, Result).
+        Records 0 .. n_out - 1 of `numbers` lie at d_out + offsets[j]; d_out may be None when out_cap is 0 (the sizing
+        call: Result.out_total is the capacity that delivers them all)."""
+        fn = self.lib.tbz_grep_records_device
+        return self._grep(lambda *a: fn(self._ctx, index._ix, d_in, in_len, *a[:4], d_out, out_cap, *a[4:]),
+                          index, pattern, first, count, max_hits)
+
     def trim(self):
         """release the context's device scratch (it only grows otherwise)"""
         self._check(self.lib.tbz_ctx_trim(self._ctx))
@@ -946,8 +997,8 @@ def grep_records(compressed, index, pattern, first=0, count=None, limit=None, en
     """which records hold `pattern` (bytes of 1 .. 32 octets): (list of record numbers, ascending; the number of matching
     records).  Records first .. first + count - 1 are searched (count None: to the last); at most `limit` numbers are
     returned, and with limit None the matching records are counted first and then all asked for.  The occurrence lies
-    wholly inside a record, its delimiter included.  decompress_records fetches the lines.  A damaged part of the stream
-    raises ThreeBzError."""
+    wholly inside a record, its delimiter included.  decompress_records fetches the lines (grep_fetch finds and fetches
+    them in one call).  A damaged part of the stream raises ThreeBzError."""
     eng = engine or index._eng
 
     def ask(max_hits):
@@ -958,4 +1009,26 @@ def grep_records(compressed, index, pattern, first=0, count=None, limit=None, en
     if limit is None:
         _, n = ask(0)
         return ask(n) if n else ([], 0)
+    return ask(limit)
+
+
+def grep_fetch(compressed, index, pattern, first=0, count=None, limit=None, max_octets=None, engine=None):
+    """the records that hold `pattern`, fetched by the search itself (one decode, where grep_records followed by
+    decompress_records takes two): (list of record numbers, ascending; records; the number of matching records).
+    `records` is a list of memoryview slices of ONE buffer, one per delivered record, delimiter included: all the numbered
+    records, or with max_octets the longest prefix of whole records within that many octets.  Records first ..
+    first + count - 1 are searched (count None: to the last); at most `limit` are numbered, and with limit None the
+    matching records are counted first and then all asked for.  A damaged part of the stream raises ThreeBzError."""
+    eng = engine or index._eng
+
+    def ask(max_hits):
+        nos, offs, buf, n, res = eng.grep_fetch(index, compressed, pattern, first, count, max_hits, max_octets)
+        if res.status < 0:
+            raise ThreeBzError(res.status, eng.strerror(res.status))
+        view = memoryview(buf)
+        k = sum(1 for o in offs[1:] if o <= res.out_len)
+        return nos, [view[offs[j]:offs[j + 1]] for j in range(k)], n
+    if limit is None:
+        _, _, n = ask(0)
+        return ask(n) if n else ([], [], 0)
     return ask(limit)

@@ -60,7 +60,8 @@ struct DevBuf {
   X(d_kc_slots) X(d_kc_ends) X(d_kc_link) X(d_kc_fm2) X(d_markers3) X(d_kb_keep) X(d_kb_kcounts) X(d_gz_cands) \
   X(d_gz_count) X(d_gz_tmp) X(d_wide_res) X(d_cold) X(d_cold2) X(d_small_rec) \
   X(d_bit_off) X(d_ix_span) X(d_ix_recs) X(d_rec_pieces) X(d_rec_queries) X(d_rec_out) \
-  X(d_srch_pieces) X(d_srch_flags) X(d_srch_hits)
+  X(d_srch_pieces) X(d_srch_flags) X(d_srch_hits) \
+  X(d_grep_pieces) X(d_grep_ends) X(d_grep_src) X(d_grep_offs) X(d_grep_sums)
 
 namespace tbz {
 // A few host threads that copy between a caller's (pageable) buffer and the pinned staging buffers: one thread moves
@@ -4585,19 +4586,48 @@ static int ix_check_args(tbz_ctx* ctx, const tbz_index* ix, size_t in_len, size_
 // plus 9 octets per input octet stays within the pool cap (ix_run's rule), and at least as far as the first record's end.
 // Its records are those whose ending delimiter lies in front of point q, so the next pass re-decodes at most interval q - 1.
 // host_in != NULL: every pass stages its span's input octets at the front of d_in_stage.
+//
+// grep (G != NULL, tbz_grep_records*): the same passes; behind the emit, the stage also packs the octets of the hits it
+// has just ranked (KG), while the run is still in the span scratch:
+//   tbz_grep_bounds over the run's pieces -> d_grep_ends, tbz_grep_spans over the flag pieces -> d_grep_src and the lengths,
+//   written where the offsets will be (d_grep_offs[done + 1 ..]); tbz_grep_sum per chunk, ONE read-back, prefix sums on the
+//   host continued from the passes before, tbz_grep_offs; tbz_grep_gather over the destination tiles of [lo, min(hi, cap)).
+// d_grep_offs holds offs[0 .. min(max_hits, records searched)] for the whole call; a pass whose first hit already lies
+// behind the capacity gathers nothing.  The host variant's destination is d_out_stage, grown as rec_run grows it.
+struct GrepCall {
+  void* d_out = nullptr;  // device variant
+  uint64_t cap = 0;
+  bool host = false;
+  uint64_t* rec_offs = nullptr;
+  uint64_t* n_out = nullptr;
+  tbz_alloc_fn alloc = nullptr;
+  void* user = nullptr;
+  uint64_t total = 0;  // octets of the hits ranked so far
+};
+static int grep_finish(tbz_ctx* ctx, GrepCall* G, uint64_t got, bool with_offs, tbz_result* res);
 static int search_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, const uint8_t* host_in, const uint8_t* pattern, size_t m,
-                      uint64_t first, uint64_t count, uint64_t* rec_nos, uint64_t max_hits, uint64_t* n_hits, tbz_result* res) {
+                      uint64_t first, uint64_t count, uint64_t* rec_nos, uint64_t max_hits, uint64_t* n_hits, tbz_result* res,
+                      GrepCall* G = nullptr) {
   memset(res, 0, sizeof *res);
   res->status = TBZ_FINISHED;
   *n_hits = 0;
+  if (G) *G->n_out = 0;
+  auto nothing = [&]() {  // no record is searched: no hit, and the h + 1 offsets are the one in front
+    if (G && max_hits) G->rec_offs[0] = 0;
+    return 0;
+  };
   for (size_t i = 0; i + 1 < m; i++)
-    if (pattern[i] == ix->delim) return 0;  // (an occurrence would straddle two records)
-  if (first >= ix->n_records || !count) return 0;
+    if (pattern[i] == ix->delim) return nothing();  // (an occurrence would straddle two records)
+  if (first >= ix->n_records || !count) return nothing();
   const uint64_t last = first + std::min<uint64_t>(count, ix->n_records - first) - 1;
   const size_t np = ix->out_off.size();
   const uint64_t room_all = std::min<uint64_t>(max_hits, last - first + 1);
   int r;
   if (room_all && (r = ensure(ctx, ctx->d_srch_hits, room_all * 8))) return r;
+  if (G && room_all) {
+    if ((r = ensure(ctx, ctx->d_grep_offs, (room_all + 1) * 8))) return r;
+    TBZ_HIP(hipMemsetAsync(ctx->d_grep_offs.p, 0, 8, ctx->stream));
+  }
   SearchMarkParams mark{};
   mark.m = (u32)m;
   mark.delim4 = (u32)ix->delim * 0x01010101u;
@@ -4644,6 +4674,7 @@ static int search_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, const
         sp[j] = SearchPiece{pieces[j].src, sum, pieces[j].len, 0u};
         sum += counts[j];
       }
+      const std::vector<SearchPiece> run_sp = G ? sp : std::vector<SearchPiece>();
       // every flag index is at most the delimiters of the run: the counts must be what the index says, or a store could
       // go behind the flags
       if (sum != nrec - (R.to_end ? 1 : 0)) return TBZ_E_INTERNAL;
@@ -4685,6 +4716,74 @@ static int search_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, const
         TBZ_LAUNCH_WG(tbz_search_emit, cnt, IX_THREADS, ctx->stream, ep);
       }
       TBZ_HIP(hipGetLastError());
+      if (!G) return 0;
+      // ---- grep: the octets of this pass's hits of rank < room
+      const uint64_t n_here = std::min(sum, room), n_delims = nrec - (R.to_end ? 1 : 0);
+      if ((rr = ensure(ctx, ctx->d_grep_ends, n_delims * 8 + 16))) return rr;
+      if ((rr = ensure(ctx, ctx->d_grep_src, n_here * 8))) return rr;
+      if ((rr = upload(ctx, ctx->d_grep_pieces, run_sp))) return rr;
+      for (size_t a = 0; a < run_sp.size(); a += MAX_GRID) {
+        const size_t cnt = std::min(MAX_GRID, run_sp.size() - a);
+        GrepBoundsParams bp{(const u8*)ctx->d_ix_span.p, (const SearchPiece*)ctx->d_grep_pieces.p + a, (const u8*)ctx->d_srch_flags.p,
+                            (u64*)ctx->d_grep_ends.p, src0, nrec, (u32)cnt, mark.delim4};
+        TBZ_LAUNCH_WG(tbz_grep_bounds, cnt, IX_THREADS, ctx->stream, bp);
+      }
+      u64* const d_offs = (u64*)ctx->d_grep_offs.p + done;  // d_offs[0]: the offset of this pass's first hit
+      for (size_t a = 0; a < sp.size(); a += MAX_GRID) {
+        const size_t cnt = std::min(MAX_GRID, sp.size() - a);
+        GrepSpansParams gp{(const u8*)ctx->d_srch_flags.p, (const SearchPiece*)ctx->d_srch_pieces.p + a, (const u64*)ctx->d_grep_ends.p,
+                           (u64*)ctx->d_grep_src.p, d_offs + 1, src0, R.len, nrec, room, (u32)cnt, R.to_end ? 1u : 0u};
+        TBZ_LAUNCH_WG(tbz_grep_spans, cnt, IX_THREADS, ctx->stream, gp);
+      }
+      const size_t n_chunks = (size_t)((n_here + GREP_CHUNK - 1) / GREP_CHUNK);
+      if ((rr = ensure(ctx, ctx->d_grep_sums, n_chunks * 16))) return rr;
+      u64* const d_sums = (u64*)ctx->d_grep_sums.p;
+      for (size_t a = 0; a < n_chunks; a += MAX_GRID) {
+        const size_t cnt = std::min(MAX_GRID, n_chunks - a);
+        GrepScanParams p{d_offs + 1 + a * GREP_CHUNK, d_sums + a, nullptr, n_here - a * GREP_CHUNK};
+        TBZ_LAUNCH_WG(tbz_grep_sum, cnt, IX_THREADS, ctx->stream, p);
+      }
+      TBZ_HIP(hipGetLastError());
+      std::vector<uint64_t> bases(n_chunks);
+      if ((rr = read_back(ctx, bases.data(), d_sums, n_chunks * 8))) return rr;
+      const uint64_t lo = G->total;
+      for (uint64_t& v : bases) {  // each chunk's sum becomes the offset of its first hit
+        const uint64_t s = v;
+        v = G->total;
+        if (s > ~0ull - G->total) return TBZ_E_INTERNAL;
+        G->total += s;
+      }
+      TBZ_HIP(hipMemcpyAsync(d_sums + n_chunks, bases.data(), n_chunks * 8, hipMemcpyHostToDevice, ctx->stream));
+      for (size_t a = 0; a < n_chunks; a += MAX_GRID) {
+        const size_t cnt = std::min(MAX_GRID, n_chunks - a);
+        GrepScanParams p{d_offs + 1 + a * GREP_CHUNK, nullptr, d_sums + n_chunks + a, n_here - a * GREP_CHUNK};
+        TBZ_LAUNCH_WG(tbz_grep_offs, cnt, IX_THREADS, ctx->stream, p);
+      }
+      TBZ_HIP(hipGetLastError());
+      if (lo >= G->cap) return 0;  // (this pass's first hit ends behind the capacity: nothing more is delivered)
+      const uint64_t hi = std::min(G->total, G->cap);
+      if (G->host && hi + 64 > ctx->d_out_stage.cap) {  // grow, keeping what earlier passes delivered
+        DevBuf old = ctx->d_out_stage;
+        ctx->d_out_stage = DevBuf{};
+        if ((rr = ensure(ctx, ctx->d_out_stage, hi + 64))) {
+          ctx->d_out_stage = old;
+          return rr;
+        }
+        if (old.p) {
+          if (lo) TBZ_HIP(hipMemcpyAsync(ctx->d_out_stage.p, old.p, lo, hipMemcpyDeviceToDevice, ctx->stream));
+          TBZ_HIP(hipStreamSynchronize(ctx->stream));
+          TBZ_HIP(hipFree(old.p));
+        }
+      }
+      u8* const dst = (u8*)(G->host ? ctx->d_out_stage.p : G->d_out);
+      const uint64_t A = (uintptr_t)dst & 15, tile_lo = (lo + A) / GREP_TILE, tile_hi = (hi + A - 1) / GREP_TILE + 1;
+      for (uint64_t a = tile_lo; a < tile_hi; a += MAX_GRID) {
+        const uint64_t cnt = std::min<uint64_t>(MAX_GRID, tile_hi - a);
+        GrepGatherParams gp{(const u8*)ctx->d_ix_span.p, dst, d_offs, (const u64*)ctx->d_grep_src.p, n_here, lo, hi, G->cap, a, (u32)cnt, 0u};
+        TBZ_LAUNCH_WG(tbz_grep_gather, cnt, IX_THREADS, ctx->stream, gp);
+      }
+      TBZ_HIP(hipGetLastError());
+      // (bases is pageable memory whose octets hipMemcpyAsync has taken; ix_run synchronises the stream after this stage)
       return 0;
     };
     void* d_out = nullptr;
@@ -4708,7 +4807,28 @@ static int search_run(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, const
   res->out_total = octets;
   res->boundary_out = start0;
   res->flags = 1u;
+  return G ? grep_finish(ctx, G, got, room_all != 0, res) : 0;
+}
+// after the last sound pass: the offsets, how many records were delivered, and (host variant) the octets
+static int grep_finish(tbz_ctx* ctx, GrepCall* G, uint64_t got, bool with_offs, tbz_result* res) {
+  int r;
+  res->out_total = 0;
+  if (!with_offs) return 0;  // (max_hits 0: counted only)
+  if ((r = read_back(ctx, G->rec_offs, ctx->d_grep_offs.p, (got + 1) * 8))) return r;
+  const uint64_t k = (uint64_t)(std::upper_bound(G->rec_offs, G->rec_offs + got + 1, G->cap) - G->rec_offs) - 1;
+  *G->n_out = k;
+  res->out_len = G->rec_offs[k];
+  res->out_total = G->rec_offs[got];
+  if (k < got) res->status = TBZ_OUTPUT_OVERFLOW;
+  if (G->host && res->out_len) {
+    uint8_t* out = G->alloc(G->user, (size_t)res->out_len);
+    if (!out) return TBZ_E_NOMEM;
+    return stage_out(ctx, out, ctx->d_out_stage.p, res->out_len);
+  }
   return 0;
+}
+static int grep_check_args(const uint64_t* rec_offs, size_t max_hits, const uint64_t* n_out) {
+  return (!n_out || (max_hits && !rec_offs)) ? TBZ_E_ARG : 0;
 }
 static int search_check_args(tbz_ctx* ctx, const tbz_index* ix, size_t in_len, const uint8_t* pattern, size_t pattern_len,
                              const uint64_t* rec_nos, size_t max_hits, const uint64_t* n_hits, const tbz_result* res) {
@@ -5160,6 +5280,43 @@ int tbz_search_records(tbz_ctx* ctx, const tbz_index* ix, const uint8_t* in, siz
   if (in_len && !in) return TBZ_E_ARG;
   TBZ_HIP(hipSetDevice(ctx->device));
   return search_run(ctx, ix, nullptr, in, pattern, pattern_len, first, count, rec_nos, max_hits, n_hits, res);
+}
+
+int tbz_grep_records_device(tbz_ctx* ctx, const tbz_index* ix, const void* d_in, size_t in_len, const uint8_t* pattern,
+                            size_t pattern_len, size_t first, size_t count, void* d_out, size_t out_cap, uint64_t* rec_nos,
+                            uint64_t* rec_offs, size_t max_hits, uint64_t* n_hits, uint64_t* n_out, tbz_result* res) {
+  using namespace tbz;
+  int r;
+  if ((r = grep_check_args(rec_offs, max_hits, n_out))) return r;
+  if ((r = search_check_args(ctx, ix, in_len, pattern, pattern_len, rec_nos, max_hits, n_hits, res))) return r;
+  if ((in_len && !d_in) || (out_cap && !d_out)) return TBZ_E_ARG;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  GrepCall G;
+  G.d_out = d_out;
+  G.cap = out_cap;
+  G.rec_offs = rec_offs;
+  G.n_out = n_out;
+  return search_run(ctx, ix, d_in, nullptr, pattern, pattern_len, first, count, rec_nos, max_hits, n_hits, res, &G);
+}
+
+int tbz_grep_records(tbz_ctx* ctx, const tbz_index* ix, const uint8_t* in, size_t in_len, const uint8_t* pattern,
+                     size_t pattern_len, size_t first, size_t count, tbz_alloc_fn alloc, void* user, size_t max_octets,
+                     uint64_t* rec_nos, uint64_t* rec_offs, size_t max_hits, uint64_t* n_hits, uint64_t* n_out, tbz_result* res) {
+  using namespace tbz;
+  int r;
+  if (!alloc) return TBZ_E_ARG;
+  if ((r = grep_check_args(rec_offs, max_hits, n_out))) return r;
+  if ((r = search_check_args(ctx, ix, in_len, pattern, pattern_len, rec_nos, max_hits, n_hits, res))) return r;
+  if (in_len && !in) return TBZ_E_ARG;
+  TBZ_HIP(hipSetDevice(ctx->device));
+  GrepCall G;
+  G.host = true;
+  G.cap = max_octets;
+  G.rec_offs = rec_offs;
+  G.n_out = n_out;
+  G.alloc = alloc;
+  G.user = user;
+  return search_run(ctx, ix, nullptr, in, pattern, pattern_len, first, count, rec_nos, max_hits, n_hits, res, &G);
 }
 
 }  // extern "C"

@@ -6084,4 +6084,279 @@ TBZ_KERNEL_WG(256, 1) void tbz_search_emit(SearchEmitParams P) {
   }
 }
 
+// ================================================================================================
+// KG — tbz_grep_bounds / _spans / _sum / _offs / _gather: the matching records' octets, packed (tbz_grep_records*).  They
+// run behind KS in the same stage, while the run still lies in the span scratch, over the flags KS has set:
+//   bounds   one more walk over the run's pieces (tbz_search_mark's walk: the delimiter ordinals carried across rounds).
+//            A delimiter octet whose record or whose successor record is flagged stores the position behind it, from the
+//            run's start, to ends[its ordinal]: one writer per entry, and no query per hit
+//   spans    tbz_search_emit's walk over the flags: the hit of rank r starts at ends[record - 1] (the run's start for its
+//            first record) and ends at ends[record] (the run's end for a last record without a delimiter), so
+//            src[r] = where it lies in the scratch and len[r] = its octets, for the ranks below the room left
+//   sum      the sum of len[] per chunk of GREP_CHUNK hits; the host reads the sums back and prefix-sums them, continuing
+//            the previous passes' total — no workgroup waits for another
+//   offs     len[] becomes, in place, the offset BEHIND each hit in the packed output: the chunk's base + a workgroup scan
+//   gather   destination-centred.  A workgroup owns a tile of GREP_TILE destination octets, cut at 16-octet boundaries of
+//            the destination ADDRESS; it finds the hits that reach into its tile by binary search in the offsets, and a
+//            lane assembles one aligned 16-octet unit per step: if the unit lies inside one hit, from the five aligned
+//            words that hold its source octets (v_alignbit; the source is an engine buffer with slack, as for tbz_ix_copy),
+//            otherwise octet by octet across the hits it spans.  A whole unit is one 16-octet store; the units at the
+//            edges of [lo, hi) and those cut by a hit that does not fit store their octets singly.  Hit j is copied iff
+//            offs[j + 1] <= cap, so the cost follows the delivered octets and nothing outside [lo, hi) is written.
+// ================================================================================================
+struct GrepBoundsParams {
+  const u8* src_base;
+  const SearchPiece* pieces;  // the run's pieces, as tbz_search_mark got them
+  const u8* flags;            // one octet per record of the run
+  u64* ends;                  // one entry per delimiter octet of the run
+  u64 run0;                   // offset in src_base of the run's first octet
+  u64 n_records;
+  u32 n_pieces;
+  u32 delim4;
+};
+struct GrepSpansParams {
+  const u8* flags;
+  const SearchPiece* pieces;  // of the flag array, as tbz_search_emit got them
+  const u64* ends;
+  u64* src;                   // per rank: offset in the span scratch of the hit's first octet
+  u64* len;                   // per rank: its octets
+  u64 run0, run_len, n_records;
+  u64 room;                   // ranks below this are written
+  u32 n_pieces;
+  u32 to_end;                 // the run's last record has no delimiter: it ends at the run's end
+};
+struct GrepScanParams {
+  u64* vals;         // n lengths; tbz_grep_offs turns them into the offsets behind each
+  u64* sums;         // tbz_grep_sum: per chunk
+  const u64* bases;  // tbz_grep_offs: per chunk, the offset of its first hit
+  u64 n;
+};
+struct GrepGatherParams {
+  const u8* src_base;
+  u8* dst;          // the caller's buffer
+  const u64* offs;  // offs[j] .. offs[j + 1]: where hit j of this pass lies in dst; offs[0] == lo
+  const u64* src;
+  u64 n_hits;       // >= 1
+  u64 lo, hi;       // the destination octets this pass may write; hi <= cap, hi <= offs[n_hits]
+  u64 cap;
+  u64 tile0;        // the first workgroup's tile, counted from the 16-aligned address at or below dst
+  u32 n_tiles;
+  u32 pad;
+};
+constexpr u32 GREP_PER_LANE = 8;
+constexpr u32 GREP_CHUNK = IX_THREADS * GREP_PER_LANE;  // hits per workgroup of sum / offs
+constexpr u32 GREP_TILE = 16u << 10;                    // destination octets per workgroup of gather: 4 steps
+
+TBZ_KERNEL_WG(256, 1) void tbz_grep_bounds(GrepBoundsParams P) {
+  TBZ_SHARED u32 s_wave[2][4];
+  const u32 r = tbz_block();
+  if (r >= P.n_pieces) return;
+  const u32 t = tbz_wave() * 64 + tbz_lane();
+  const SearchPiece R = P.pieces[r];
+  const u8* s = P.src_base + R.src;
+  const u32 k = (u32)((uintptr_t)s & 15), n = R.len;
+  const u8* al = s - k;
+  const u32 lines = (k + n + 15) >> 4;
+  const u32 chunks = (lines + 3) >> 2;
+  const u64 al_rel = R.src - k - P.run0;  // `al` from the run's start (wraps for the first piece; the sums below do not)
+  u64 carry = R.base;
+  for (u32 c0 = 0; c0 < chunks; c0 += IX_THREADS) {
+    const u32 ch = c0 + t;
+    u64 same = 0, dl = 0;
+    if (ch < chunks) search_chunk(al, ch, k, n, lines, P.delim4, P.delim4, same, dl);
+    u32 total;
+    const u32 excl = search_wg_scan(s_wave, (c0 / IX_THREADS) & 1, tbz_popc64(dl), total);
+    u64 d = carry + excl;  // ordinal of this lane's first delimiter octet == the record it ends
+    u32 mine = dl ? P.flags[d] : 0u;
+    while (dl) {
+      const u32 b = tbz_ffs64(dl) - 1;
+      dl &= dl - 1;
+      const u32 next = d + 1 < P.n_records ? P.flags[d + 1] : 0u;
+      if (mine | next) P.ends[d] = al_rel + (u64)ch * REC_CHUNK + b + 1;
+      mine = next;
+      d++;
+    }
+    carry += total;
+  }
+}
+
+TBZ_KERNEL_WG(256, 1) void tbz_grep_spans(GrepSpansParams P) {
+  TBZ_SHARED u32 s_wave[2][4];
+  const u32 r = tbz_block();
+  if (r >= P.n_pieces) return;
+  const u32 t = tbz_wave() * 64 + tbz_lane();
+  const SearchPiece R = P.pieces[r];
+  const u8* s = P.flags + R.src;
+  const u32 k = (u32)((uintptr_t)s & 15), n = R.len;
+  const u8* al = s - k;
+  const u32 lines = (k + n + 15) >> 4;
+  const u32 chunks = (lines + 3) >> 2;
+  u64 carry = R.base;
+  for (u32 c0 = 0; c0 < chunks; c0 += IX_THREADS) {
+    const u32 ch = c0 + t;
+    u64 set = 0, same = 0;
+    if (ch < chunks) search_chunk(al, ch, k, n, lines, 0x01010101u, 0x01010101u, set, same);
+    u32 total;
+    const u32 excl = search_wg_scan(s_wave, (c0 / IX_THREADS) & 1, tbz_popc64(set), total);
+    u64 rank = carry + excl;
+    while (set && rank < P.room) {
+      const u32 b = tbz_ffs64(set) - 1;
+      set &= set - 1;
+      const u64 rec = R.src + ((u64)ch * REC_CHUNK + b - k);  // within the run
+      const u64 from = rec ? P.ends[rec - 1] : 0;
+      const u64 to = (P.to_end && rec + 1 == P.n_records) ? P.run_len : P.ends[rec];
+      P.src[rank] = P.run0 + from;
+      P.len[rank] = to - from;
+      rank++;
+    }
+    carry += total;
+  }
+}
+
+TBZ_DEV u64 grep_wave_incl_scan_u64(u64 x) {
+  const u32 lane = tbz_lane();
+#pragma unroll
+  for (u32 d = 1; d < 64; d <<= 1) {
+    const u64 y = tbz_shfl_up64(x, d);
+    if (lane >= d) x += y;
+  }
+  return x;
+}
+// the workgroup's exclusive scan of c in lane order, and the total
+TBZ_DEV u64 grep_wg_scan_u64(u64* s_wave, u64 c, u64& total) {
+  const u32 w = tbz_wave();
+  const u64 incl = grep_wave_incl_scan_u64(c);
+  if (tbz_lane() == 63) s_wave[w] = incl;
+  tbz_wg_barrier();
+  const u64 t0 = s_wave[0], t1 = s_wave[1], t2 = s_wave[2], t3 = s_wave[3];
+  total = t0 + t1 + t2 + t3;
+  return incl - c + (w > 0 ? t0 : 0ull) + (w > 1 ? t1 : 0ull) + (w > 2 ? t2 : 0ull);
+}
+
+TBZ_KERNEL_WG(256, 1) void tbz_grep_sum(GrepScanParams P) {
+  TBZ_SHARED u64 s_wave[4];
+  const u32 r = tbz_block();
+  const u32 t = tbz_wave() * 64 + tbz_lane();
+  const u64 at = (u64)r * GREP_CHUNK + (u64)t * GREP_PER_LANE;
+  u64 c = 0;
+#pragma unroll
+  for (u32 i = 0; i < GREP_PER_LANE; i++)
+    if (at + i < P.n) c += P.vals[at + i];
+  u64 total;
+  grep_wg_scan_u64(s_wave, c, total);
+  if (t == 0) P.sums[r] = total;
+}
+
+TBZ_KERNEL_WG(256, 1) void tbz_grep_offs(GrepScanParams P) {
+  TBZ_SHARED u64 s_wave[4];
+  const u32 r = tbz_block();
+  const u32 t = tbz_wave() * 64 + tbz_lane();
+  const u64 at = (u64)r * GREP_CHUNK + (u64)t * GREP_PER_LANE;
+  u64 v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0, v7 = 0;
+  if (at + 0 < P.n) v0 = P.vals[at + 0];
+  if (at + 1 < P.n) v1 = P.vals[at + 1];
+  if (at + 2 < P.n) v2 = P.vals[at + 2];
+  if (at + 3 < P.n) v3 = P.vals[at + 3];
+  if (at + 4 < P.n) v4 = P.vals[at + 4];
+  if (at + 5 < P.n) v5 = P.vals[at + 5];
+  if (at + 6 < P.n) v6 = P.vals[at + 6];
+  if (at + 7 < P.n) v7 = P.vals[at + 7];
+  v1 += v0; v2 += v1; v3 += v2; v4 += v3; v5 += v4; v6 += v5; v7 += v6;
+  u64 total;
+  const u64 base = P.bases[r] + grep_wg_scan_u64(s_wave, v7, total);
+  if (at + 0 < P.n) P.vals[at + 0] = base + v0;
+  if (at + 1 < P.n) P.vals[at + 1] = base + v1;
+  if (at + 2 < P.n) P.vals[at + 2] = base + v2;
+  if (at + 3 < P.n) P.vals[at + 3] = base + v3;
+  if (at + 4 < P.n) P.vals[at + 4] = base + v4;
+  if (at + 5 < P.n) P.vals[at + 5] = base + v5;
+  if (at + 6 < P.n) P.vals[at + 6] = base + v6;
+  if (at + 7 < P.n) P.vals[at + 7] = base + v7;
+}
+
+// the largest j in [lo, hi] with offs[j] <= pos (offs ascending, offs[lo] <= pos)
+TBZ_DEV u64 grep_find(const u64* offs, u64 lo, u64 hi, u64 pos) {
+  while (lo < hi) {
+    const u64 mid = lo + (hi - lo + 1) / 2;
+    if (offs[mid] <= pos) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+TBZ_KERNEL_WG(256, 1) void tbz_grep_gather(GrepGatherParams P) {
+  const u32 r = tbz_block();
+  if (r >= P.n_tiles) return;
+  const u32 t = tbz_wave() * 64 + tbz_lane();
+  // positions `g` count from the 16-aligned address at or below dst: g = destination offset + A
+  const u64 A = (u64)((uintptr_t)P.dst & 15);
+  const u64 g_lo = P.lo + A, g_hi = P.hi + A;
+  const u64 t_lo = (P.tile0 + r) * GREP_TILE, t_hi = t_lo + GREP_TILE;
+  const u64 ta = t_lo > g_lo ? t_lo : g_lo, te = t_hi < g_hi ? t_hi : g_hi;
+  if (ta >= te) return;
+  // the hits that reach into the tile (the same in every lane)
+  const u64 j_first = grep_find(P.offs, 0, P.n_hits - 1, ta - A);
+  const u64 j_last = grep_find(P.offs, j_first, P.n_hits - 1, te - 1 - A);
+  for (u64 g = t_lo + (u64)t * 16; g < te; g += (u64)IX_THREADS * 16) {
+    const u64 a = g > g_lo ? g : g_lo, e = g + 16 < g_hi ? g + 16 : g_hi;
+    if (a >= e) continue;
+    const u64 pa = a - A, pe = e - A;  // destination offsets of the unit's octets
+    u64 j = grep_find(P.offs, j_first, j_last, pa);
+    u64 oj = P.offs[j], oj1 = P.offs[j + 1], sj = P.src[j];
+    if (oj1 > P.cap) continue;  // (nor does any later hit fit)
+    if (e - a == 16 && oj1 >= pe) {  // a whole unit inside one hit
+      const u8* s = P.src_base + sj + (pa - oj);
+      const u32 sh = (u32)((uintptr_t)s & 3) * 8;
+      const u32* q = (const u32*)(s - ((uintptr_t)s & 3));
+      const u32 w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = q[4];
+      tbz_u32x4 o;
+      o.x = tbz_alignbit(w1, w0, sh);
+      o.y = tbz_alignbit(w2, w1, sh);
+      o.z = tbz_alignbit(w3, w2, sh);
+      o.w = tbz_alignbit(w4, w3, sh);
+      *(tbz_u32x4*)(P.dst + pa) = o;
+      continue;
+    }
+    // across hits, or a unit cut by [lo, hi): octet i of the unit is destination offset g - A + i
+    u32 x0 = 0, x1 = 0, x2 = 0, x3 = 0, have = 0;
+    bool fits = true;
+#pragma unroll
+    for (u32 i = 0; i < 16; i++) {
+      const u64 pos = g + i - A;  // (wraps in front of dst; such octets are outside [a, e))
+      if (fits && g + i >= a && g + i < e) {
+        while (pos >= oj1) {
+          j++;
+          oj = oj1;
+          oj1 = P.offs[j + 1];
+          sj = P.src[j];
+        }
+        fits = oj1 <= P.cap;
+        if (fits) {
+          const u32 v = (u32)P.src_base[sj + (pos - oj)] << (8 * (i & 3));
+          if ((i >> 2) == 0) x0 |= v;
+          if ((i >> 2) == 1) x1 |= v;
+          if ((i >> 2) == 2) x2 |= v;
+          if ((i >> 2) == 3) x3 |= v;
+          have |= 1u << i;
+        }
+      }
+    }
+    if (have == 0xffffu) {
+      tbz_u32x4 o;
+      o.x = x0;
+      o.y = x1;
+      o.z = x2;
+      o.w = x3;
+      *(tbz_u32x4*)(P.dst + pa) = o;
+    } else {
+#pragma unroll
+      for (u32 i = 0; i < 16; i++)
+        if (have & (1u << i)) {
+          const u32 w = (i >> 2) == 0 ? x0 : (i >> 2) == 1 ? x1 : (i >> 2) == 2 ? x2 : x3;
+          P.dst[g + i - A] = (u8)(w >> (8 * (i & 3)));
+        }
+    }
+  }
+}
+
 }  // namespace tbz

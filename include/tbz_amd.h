@@ -424,6 +424,50 @@ int tbz_search_records(tbz_ctx* ctx, const tbz_index* index, const uint8_t* in, 
                        size_t pattern_len, size_t first, size_t count, uint64_t* rec_nos, size_t max_hits, uint64_t* n_hits,
                        tbz_result* res);
 
+/* ---- grep: the matching records themselves ------------------------------------------------------------
+ * (Additive: TBZ_ABI_VERSION stays 4.)  One call searches exactly as tbz_search_records* does — the pattern, the match
+ * rule, the pattern with an inner delimiter decided on the host, the clipping of first / count, the ascending passes of
+ * whole records under the pool cap and the per-interval crc and delimiter-count checks are those of the search section —
+ * and, from the same pass, packs the matching records' octets in ascending record order into a buffer on the device.
+ * *n_hits = the number of matching records among those searched, also those beyond max_hits.  With
+ * h = min(*n_hits, max_hits) and len[j] the octets of the j-th matching record, its delimiter included where it has one:
+ *   rec_nos[0 .. h)    the record numbers, ascending: what tbz_search_records writes
+ *   rec_offs[0 .. h]   h + 1 entries, rec_offs[0] = 0 and rec_offs[j + 1] = rec_offs[j] + len[j]: where the records lie
+ *                      in a buffer that holds all h back to back.  They do not depend on the capacity.  The caller
+ *                      provides max_hits + 1 entries; nothing behind rec_offs[h] is written.
+ *   *n_out = k         the largest k <= h with rec_offs[k] <= out_cap (host variant: <= max_octets).  Delivery is in whole
+ *                      records and is a prefix: records 0 .. k - 1 are delivered, record j as
+ *                      d_out[rec_offs[j] .. rec_offs[j + 1]), contiguous, no padding: the octets grep would print.
+ *                      Nothing at or behind d_out + rec_offs[k] and nothing in front of d_out is written; d_out may have
+ *                      any alignment.
+ * res: status TBZ_FINISHED, or TBZ_OUTPUT_OVERFLOW when k < h, or the first failed span's error as search reports it;
+ * out_len = rec_offs[k]; out_total = rec_offs[h], the capacity that delivers all h records — NOT the octets searched, as
+ * it is for tbz_search_records; boundary_out, segments, in_consumed and flags as for search.
+ * Sizing: max_hits == 0 with rec_nos == rec_offs == NULL counts only (out_total = 0).  d_out may be NULL when
+ * out_cap == 0, and a call with out_cap == 0 and max_hits > 0 is the sizing call: numbers, offsets and out_total, no octet.
+ * A failed span (damage, a lying index): *n_hits = *n_out = 0, out_len = out_total = 0, nothing is written to rec_nos /
+ * rec_offs, and the host variant does not call alloc.  Device variant: octets of d_out[0 .. out_cap) may have been written
+ * by the passes before the failed one; nothing outside that range is written.
+ * Host variant: alloc(user, out_len) is called once, after the last pass is sound, and only if out_len > 0; the octets
+ * are staged on the device across passes.  max_octets = SIZE_MAX: no limit.  Only the spans' input octets go to the
+ * device; only the delivered octets, the two arrays and the result words come back; the host never sees another decoded
+ * octet and never scans octets (it sums per-piece counts and per-chunk lengths).
+ * Once a record does not fit, later passes still search (n_hits is a total) and still rank their hits below max_hits
+ * (the offsets are complete), but gather nothing.
+ * Device memory on top of a pass's decode and of what search takes (1 octet per record of the pass, 8 per
+ * min(max_hits, records searched)): 8 octets per record of the pass (the positions behind its delimiters), 16 octets per
+ * hit of the pass below max_hits (source offset; chunk sums and bases add 16 per 2048 hits), and 8 octets per
+ * min(max_hits, records searched) + 1 for the offsets of the whole call.  Host variant: the delivered octets + 64 as well.
+ * TBZ_E_ARG: every case of tbz_search_records*; a NULL rec_nos or rec_offs with max_hits > 0; a NULL n_hits, n_out or
+ * res; a NULL d_out with out_cap > 0; a NULL alloc (host variant).  TBZ_E_UNSUPPORTED with TBZ_HIST=off. */
+int tbz_grep_records_device(tbz_ctx* ctx, const tbz_index* index, const void* d_in, size_t in_len, const uint8_t* pattern,
+                            size_t pattern_len, size_t first, size_t count, void* d_out, size_t out_cap, uint64_t* rec_nos,
+                            uint64_t* rec_offs, size_t max_hits, uint64_t* n_hits, uint64_t* n_out, tbz_result* res);
+int tbz_grep_records(tbz_ctx* ctx, const tbz_index* index, const uint8_t* in, size_t in_len, const uint8_t* pattern,
+                     size_t pattern_len, size_t first, size_t count, tbz_alloc_fn alloc, void* user, size_t max_octets,
+                     uint64_t* rec_nos, uint64_t* rec_offs, size_t max_hits, uint64_t* n_hits, uint64_t* n_out,
+                     tbz_result* res);
+
 /* ---- gzip header metadata (host side; no device involved) --------------------------------------
  * What decompress-gzip leaves in the gzip-state's slots while it reads the header (gzip.lisp:110-266:
  * compression-method, flags, mtime, compression level, operating system, extra / name / comment fields, header CRC).

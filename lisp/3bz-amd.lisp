@@ -43,6 +43,7 @@
    #:index-records #:decompress-records
    ;; ---- ... and the numbers of the records that hold a pattern
    #:search-records
+   #:grep-records
    ;; ---- beyond the reference (SURVEY §8e): many independent streams over the GPUs of one node, from ONE Lisp process
    #:*engines* #:open-engines #:close-engines #:decompress-vectors))
 (in-package #:3bz-amd)
@@ -143,6 +144,11 @@
 (cffi:defcfun ("tbz_search_records" %search-records) :int
   (ctx :pointer) (index :pointer) (in :pointer) (in-len :size) (pattern :pointer) (pattern-len :size) (first :size)
   (count :size) (rec-nos :pointer) (max-hits :size) (n-hits :pointer) (res :pointer))
+;;; grep: the same search, and the matching records' octets packed from the same pass
+(cffi:defcfun ("tbz_grep_records" %grep-records) :int
+  (ctx :pointer) (index :pointer) (in :pointer) (in-len :size) (pattern :pointer) (pattern-len :size) (first :size)
+  (count :size) (alloc :pointer) (user :pointer) (max-octets :size) (rec-nos :pointer) (rec-offs :pointer) (max-hits :size)
+  (n-hits :pointer) (n-out :pointer) (res :pointer))
 
 (deftype octet () '(unsigned-byte 8))
 (deftype octet-vector () '(simple-array octet (*)))
@@ -510,6 +516,55 @@ go there, only the numbers come back."
           (let ((n (nth-value 1 (ask 0))))   ; (count first; nothing to fetch when nothing matched)
             (if (zerop n)
                 (values (make-array 0 :element-type '(unsigned-byte 64)) 0)
+                (ask n)))))))
+
+(defun grep-records (compressed index pattern &key (first 0) count limit max-octets)
+  "The records of the stream's OUTPUT that hold PATTERN (an octet vector of 1 .. 32 octets): their numbers, ascending, as a
+vector of (unsigned-byte 64), a list of octet vectors, one per delivered record with its delimiter, and the number of
+matching records as the third value.  Records FIRST .. FIRST + COUNT - 1 are searched (COUNT nil: to the last record); at
+most LIMIT are numbered (nil: the matching records are counted first, then all asked for); with MAX-OCTETS the records
+delivered are the longest prefix of whole records within that many octets (nil: all numbered records).  One decode finds
+the records and fetches them, where SEARCH-RECORDS followed by DECOMPRESS-RECORDS takes two: the octets are packed on the
+device, and only they, the numbers and their offsets come back."
+  (unless (<= 1 (length pattern) 32) (error "a pattern is 1 .. 32 octets"))
+  (let ((count (or count (nth-value 1 (index-records index))))
+        (pat (coerce pattern 'octet-vector))
+        (cap (or max-octets (1- (ash 1 (* 8 (cffi:foreign-type-size :size)))))))
+    (flet ((ask (max-hits)
+             (let ((numbers (make-array max-hits :element-type '(unsigned-byte 64)))
+                   (offsets (make-array (1+ max-hits) :element-type '(unsigned-byte 64)))
+                   (*alloc-results* nil))
+               (cffi:with-foreign-objects ((res '(:struct tbz-result)) (n-hits :uint64) (n-out :uint64))
+                 (unwind-protect
+                      (progn
+                        (cffi:with-pointer-to-vector-data (pin compressed)
+                          (cffi:with-pointer-to-vector-data (ppat pat)
+                            (cffi:with-pointer-to-vector-data (pnos numbers)
+                              (cffi:with-pointer-to-vector-data (poffs offsets)
+                                (check-call (%grep-records (engine) index pin (length compressed) ppat (length pat) first count
+                                                           (cffi:callback alloc-octets) (cffi:null-pointer) cap
+                                                           (if (zerop max-hits) (cffi:null-pointer) pnos)
+                                                           (if (zerop max-hits) (cffi:null-pointer) poffs)
+                                                           max-hits n-hits n-out res)
+                                            "tbz_grep_records")))))
+                        (let ((status (cffi:foreign-slot-value res '(:struct tbz-result) 'status))
+                              (n (cffi:mem-ref n-hits :uint64))
+                              (k (cffi:mem-ref n-out :uint64)))
+                          (when (minusp status) (error "~a" (%strerror status)))
+                          (let ((octets (if *alloc-results*
+                                            (take-alloc-result (first *alloc-results*))
+                                            (make-array 0 :element-type 'octet))))
+                            (values (if (< n max-hits) (subseq numbers 0 n) numbers)
+                                    (loop for j below k
+                                          collect (subseq octets (aref offsets j) (aref offsets (1+ j))))
+                                    n))))
+                   (dolist (cell *alloc-results*)   ; (handed out and not taken: given back)
+                     (unless (cffi:null-pointer-p (car cell)) (cffi:foreign-free (car cell)))))))))
+      (if limit
+          (ask limit)
+          (let ((n (nth-value 2 (ask 0))))   ; (count first; nothing to fetch when nothing matched)
+            (if (zerop n)
+                (values (make-array 0 :element-type '(unsigned-byte 64)) nil 0)
                 (ask n)))))))
 
 ;;; ---- every member of a multi-member .gz (SURVEY §8f-4; 3bz stops after the first: gzip.lisp:277-286) ----
